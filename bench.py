@@ -16,6 +16,15 @@ WORLD_SIZE in the environment this process starts torch.distributed.run with
 N workers (one per GPU, RCCL backend "nccl") as a child, before touching the
 GPU; under torch.distributed.run directly it is one of the N ranks.  Rank 0
 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed
+steps, the result line (metric, value, unit, ms_per_step, dtype, config, the
+end-to-end MFMA fraction).  --dump-outputs DIR also writes what the last timed
+step returned as DIR/<name>.npy.  --full adds every secondary measurement and
+check to the line: the live c_fc roofline (event-instrumented extra steps),
+the small-chunk bit-identity check of the timed rows, per-kernel timings,
+preprocessing / JPEG ingest, the rank roofline, the fp32 parity mode and the
+CPU baseline (the --no-* switches drop single legs of a --full run).
 """
 from __future__ import annotations
 
@@ -47,6 +56,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements and checks (live roofline, "
+                         "bit-identity check, kernel timings, ingest, rank roofline, parity mode, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (image embeddings, text embeddings, top-k "
+                         "scores and indices) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--model", default="ViT-B/32")
     ap.add_argument("--frames", type=int, default=10_000, help="frames per GPU (weak scaling: each rank's shard)")
     ap.add_argument("--global-frames", type=int, default=None,
@@ -75,7 +90,10 @@ def parse():
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="the N > 1 process group: nccl (RCCL over xGMI, the measured path) or gloo (a rehearsal "
                          "of the multi-rank step on fewer GPUs than ranks: rank r uses GPU r %% device_count)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def lnfold_active(model, cfg):
@@ -602,6 +620,70 @@ def parity_mode(args, dev, pixels, tokens, Q, k, base, chunk):
     return out
 
 
+def secondary_timings(args, model, cfg, chunk, tokens, emb, k, dev):
+    """--full: the per-kernel timings, preprocessing, JPEG ingest and the rank roofline."""
+    import torch
+    _progress("kernel timings")
+    kern = {} if args.no_kernel_timing else kernel_timing(model, cfg, chunk)
+    txt = model.encode_text(tokens, normalize=True, out_dtype=torch.float32)
+    kern["rank_topk"] = rank_timing(emb, txt, k)
+    kern["preprocess_720p"] = preprocess_timing(dev, cfg.image_resolution)
+    ingest = jpeg_ingest_timing(dev, cfg.image_resolution)
+    if ingest:
+        kern["jpeg_ingest_720p"] = ingest
+    _progress("rank roofline")
+    rank_roof = None if args.no_rank_roofline else rank_roofline(dev)
+    return kern, rank_roof
+
+
+def verify_rows(model, pixels, emb, Nf, dev):
+    """Outside the timed region: the timed pass's rows at tile / XCD-range / 2^31-offset / last-tile
+    frames (tests/test_gpu_bench_config.py) re-encoded as one small chunk must be bit-identical
+    (every kernel's per-row arithmetic is independent of the pass size); the CPU baseline leg
+    checks the same rows against the torch-CPU fp32 restatement.
+    At least 8 frames, so that the re-encode's B * S rows fill the 256-row tiles the LayerNorm-folded
+    GEMMs need, as the timed pass does: 5 B/32 frames = 250 rows take the unfolded tower, whose
+    products round differently -- seen with --frames 4000."""
+    import torch
+    vidx = sorted({f for f in (0, 5, 1250, 2500, 4999, 6990, 9320, Nf - 1) if f < Nf})
+    for f in range(Nf):
+        if len(vidx) >= 8:
+            break
+        if f not in vidx:
+            vidx.append(f)
+    vidx = sorted(vidx)
+    vt = torch.tensor(vidx, device=dev)
+    emb_v = emb[vt].cpu()
+    again = model.encode_image(pixels[vt], out_dtype=torch.float32).cpu()
+    verify = {"frames": vidx, "single_pass_equals_small_chunk": bool(torch.equal(emb_v, again))}
+    assert verify["single_pass_equals_small_chunk"], "timed pass rows differ from a small-chunk re-encode"
+    return verify, vt, emb_v
+
+
+def dump_outputs(out_dir, emb, txt, top_s, top_i):
+    """--dump-outputs: what the last timed step returned, as <out_dir>/<name>.npy for an
+    output-for-output comparison of two builds (the inputs are seeded, so equal arguments give
+    equal inputs): image_embeddings [N,D] and text_embeddings [Q,D] float32, topk_scores [Q,k]
+    float32, topk_indices [Q,k] float64 (exact: indices are far below 2^53).  An array above its
+    share of the 64 MB limit is written as a fixed sample of its rows (numpy default_rng(0),
+    ascending), with the rows' numbers beside it in <name>_rows.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    mib = 1 << 20
+    for name, t, dtype, budget in (("image_embeddings", emb, np.float32, 36 * mib),
+                                   ("text_embeddings", txt, np.float32, 4 * mib),
+                                   ("topk_scores", top_s, np.float32, 4 * mib),
+                                   ("topk_indices", top_i, np.float64, 4 * mib)):
+        n = t.shape[0]
+        keep = max(1, budget // max(1, (t.numel() // max(1, n)) * np.dtype(dtype).itemsize))
+        if n > keep:
+            rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(dtype))
+
+
 def launch_workers(args):
     """`bench.py --gpus N` without torch.distributed.run: start N worker
     processes (one per GPU) through torch.distributed.run as a CHILD process,
@@ -711,8 +793,8 @@ def main():
         emb = model.encode_image(pixels, out_dtype=torch.float32)
         txt = model.encode_text(tokens, normalize=True, out_dtype=torch.float32)
         if world > 1:
-            return emb, distributed.sharded_topk(emb, txt, k, base)
-        return emb, retrieval.rank_topk(emb, txt, k, index_base=base)
+            return emb, distributed.sharded_topk(emb, txt, k, base), txt
+        return emb, retrieval.rank_topk(emb, txt, k, index_base=base), txt
 
     for _ in range(args.warmup):
         step()
@@ -723,19 +805,21 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        emb, (top_s, top_i) = step()
+        emb, (top_s, top_i), txt_out = step()
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:    # before anything else runs on the model
+        dump_outputs(args.dump_outputs, emb, txt_out, top_s, top_i)
     # the roofline kernel (mlp.c_fc of the LayerNorm-folded bf16 tower) timed live: HIP events on the
     # launch stream around each of its launches (mi_clip_kernel_events) in `ev_steps` further steps of
-    # the same workload run AFTER the timed loop, so the timed steps carry no event records
+    # the same workload run AFTER the timed loop, so the timed steps carry no event records (--full)
     ev_steps = min(args.steps, 5)
     n_fc = min(ev_steps * cfg.vision_layers * (-(-Nf // chunk)), 1 << 16)   # the library's event capacity
     fc_us = None
-    if lnfold_active(model, cfg) and not args.no_kernel_timing:
+    if args.full and lnfold_active(model, cfg) and not args.no_kernel_timing:
         import ctypes
         _N.check(_N.lib().mi_clip_kernel_events(model._ctx, 1, n_fc), "mi_clip_kernel_events")
         for _ in range(ev_steps):
@@ -753,41 +837,17 @@ def main():
         elapsed = t.item()
         seen = dist.get_world_size()
     assert torch.isfinite(top_s[:, 0]).all() and (top_i[:, 0] >= 0).all()
-    # outside the timed region: the timed pass's rows at tile / XCD-range / 2^31-offset / last-tile
-    # frames (tests/test_gpu_bench_config.py) re-encoded as one small chunk must be bit-identical
-    # (every kernel's per-row arithmetic is independent of the pass size); the CPU baseline leg
-    # checks the same rows against the torch-CPU fp32 restatement
-    # (at least 8 frames, so that the re-encode's B * S rows fill the 256-row tiles the LayerNorm-folded
-    # GEMMs need, as the timed pass does: 5 B/32 frames = 250 rows take the unfolded tower, whose
-    # products round differently -- seen with --frames 4000)
-    vidx = sorted({f for f in (0, 5, 1250, 2500, 4999, 6990, 9320, Nf - 1) if f < Nf})
-    for f in range(Nf):
-        if len(vidx) >= 8:
-            break
-        if f not in vidx:
-            vidx.append(f)
-    vidx = sorted(vidx)
-    vt = torch.tensor(vidx, device=dev)
-    emb_v = emb[vt].cpu()
-    again = model.encode_image(pixels[vt], out_dtype=torch.float32).cpu()
-    verify = {"frames": vidx, "single_pass_equals_small_chunk": bool(torch.equal(emb_v, again))}
-    assert verify["single_pass_equals_small_chunk"], "timed pass rows differ from a small-chunk re-encode"
+    verify = vt = emb_v = None
+    if args.full:
+        verify, vt, emb_v = verify_rows(model, pixels, emb, Nf, dev)
 
     ms = elapsed / args.steps * 1e3
     total_frames = (args.global_frames if strong else Nf * world) * args.steps
     value = total_frames / elapsed
     result = None
     if rank == 0:
-        _progress(f"timed {args.steps} steps: {ms:.2f} ms/step; kernel timings")
-        kern = {} if args.no_kernel_timing else kernel_timing(model, cfg, chunk)
-        txt = model.encode_text(tokens, normalize=True, out_dtype=torch.float32)
-        kern["rank_topk"] = rank_timing(emb, txt, k)
-        kern["preprocess_720p"] = preprocess_timing(dev, cfg.image_resolution)
-        ingest = jpeg_ingest_timing(dev, cfg.image_resolution)
-        if ingest:
-            kern["jpeg_ingest_720p"] = ingest
-        _progress("rank roofline")
-        rank_roof = None if args.no_rank_roofline else rank_roofline(dev)
+        _progress(f"timed {args.steps} steps: {ms:.2f} ms/step")
+        kern, rank_roof = secondary_timings(args, model, cfg, chunk, tokens, emb, k, dev) if args.full else ({}, None)
         # executed work (step_work: the CLS-row last block of the bf16, MX-fp8 and fp32 towers at >= 256
         # frames per chunk) at its engines' dense peaks over the step time, per rank
         work = step_work(cfg, args.weights, chunk, lnfold_active(model, cfg))
@@ -834,11 +894,12 @@ def main():
                                f"micro loop (kernels.gemm_fc) {dom['micro_us']} us") if "launches" in dom
                               else "HIP events around the kernel_timing micro loop (random operands)"}
         parity = None
-        _progress("parity mode / cpu baseline")
-        if not args.no_parity_mode and world == 1 and args.weights == "bf16":
+        if args.full:
+            _progress("parity mode / cpu baseline")
+        if args.full and not args.no_parity_mode and world == 1 and args.weights == "bf16":
             parity = parity_mode(args, dev, pixels, tokens, Q, k, base, chunk)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(cfg, Nf, Q, k, args.cpu_frames_b1, args.cpu_frames,
                                check=(pixels[vt].float().cpu().numpy(), emb_v.numpy()))
             verify["gpu_rows_vs_cpu_fp32_min_cosine"] = cpu.pop("check_min_cosine", None)
@@ -856,6 +917,7 @@ def main():
             "metric": "frames/sec embedded+ranked, ViT-B/32 224², 1/2/4/8 MI355X; R@1/5/10 parity",
             "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "world_size_seen": seen, "build_id": _N.lib().mi_build_id().decode(),
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
+            "full": args.full,
             "scaling": "strong" if strong else "weak", "vs_baseline": None,
             "dtype": {"bf16": "bf16", "fp32": "f32"}.get(args.weights, "fp8-e4m3(MX) vision GEMMs, bf16 rest"),
             "data": "synthetic (random pixels/tokens, deterministic random-init weights of the real architecture)",
@@ -874,6 +936,9 @@ def main():
             "kernels": kern,
             "cpu_baseline": cpu,
         }
+        if not args.full:   # a plain run carries the headline only
+            for key in ("roofline", "rank_roofline", "parity_mode", "verify", "kernels", "cpu_baseline"):
+                del result[key]
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

@@ -38,4 +38,10 @@ def gpu():
 
 
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """A fixture under tests/golden; a .npz whose largest array was stored beside it as
+    <stem>.part2.npz (make_golden.py save_split: no file above 1 MiB) is read as one mapping."""
+    d = np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    part2 = os.path.join(GOLDEN, name[:-4] + ".part2.npz")
+    if name.endswith(".npz") and os.path.exists(part2):
+        d = {**{k: d[k] for k in d.files}, **np.load(part2, allow_pickle=False)}
+    return d

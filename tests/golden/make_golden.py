@@ -37,6 +37,20 @@ REF_CORPUS = "/root/reference/Backend/embedding/video_test_4_embeddings.npy"
 # video_test_3 in metadata/video_mapping.json:2-4, or to image_embeddings.npy): float16 rows
 REF_CORPUS_F16 = "/root/reference/Backend/embedding/video_test_3_embeddings.npy"
 REF_IMAGE_EMB = "/root/reference/Backend/embedding/image_embeddings.npy"
+FILE_LIMIT = 1 << 20   # no committed file above 1 MiB
+
+
+def save_split(path, **arrays):
+    """np.savez_compressed, with the largest array moved to <stem>.part2.npz when the file would
+    exceed FILE_LIMIT (tests/conftest.py golden() reads the two as one)."""
+    part2 = path[:-4] + ".part2.npz"
+    np.savez_compressed(path, **arrays)
+    if os.path.getsize(path) > FILE_LIMIT:
+        big = max(arrays, key=lambda k: np.asarray(arrays[k]).nbytes)
+        np.savez_compressed(path, **{k: v for k, v in arrays.items() if k != big})
+        np.savez_compressed(part2, **{big: arrays[big]})
+    elif os.path.exists(part2):
+        os.remove(part2)
 
 
 def encoder_golden(name, n_img, n_txt):
@@ -128,8 +142,8 @@ def fp16_rank_golden(nq=200, seed=2024):
     print("f32-normalised ranking differs on", np.any(f32norm != out["top_index_60"], axis=1).sum(), "/", nq,
           "top-60 lists;", np.any(f32norm[:, :10] != out["top_index_10"], axis=1).sum(), "top-10")
     path = os.path.join(HERE, "rank_video_test_3.npz")
-    np.savez_compressed(path, corpus=raw, queries=q, normalized=E16, image_embeddings_identical=image_same,
-                        seed=seed, **out)
+    save_split(path, corpus=raw, queries=q, normalized=E16, image_embeddings_identical=image_same,
+               seed=seed, **out)
     print("wrote", path, "image_embeddings.npy byte-identical:", image_same)
 
 
@@ -163,10 +177,10 @@ def rk_golden():
             break
     ref = rank_ref.retrieval_metrics_ref(img.astype(np.float32), txt, list(cap_ids), list(range(n_img)))
     out = os.path.join(HERE, "rk_flow.npz")
-    np.savez_compressed(out, image_features=img.astype(np.float32), text_features=txt, caption_image_ids=cap_ids,
-                        image_ids=np.arange(n_img), t2i_ranks=ref["t2i_ranks"], i2t_ranks=ref["i2t_ranks"],
-                        t2i_r=np.array([ref["t2i"]["R@1"], ref["t2i"]["R@5"], ref["t2i"]["R@10"]]),
-                        i2t_r=np.array([ref["i2t"]["R@1"], ref["i2t"]["R@5"], ref["i2t"]["R@10"]]), seed=seed)
+    save_split(out, image_features=img.astype(np.float32), text_features=txt, caption_image_ids=cap_ids,
+               image_ids=np.arange(n_img), t2i_ranks=ref["t2i_ranks"], i2t_ranks=ref["i2t_ranks"],
+               t2i_r=np.array([ref["t2i"]["R@1"], ref["t2i"]["R@5"], ref["t2i"]["R@10"]]),
+               i2t_r=np.array([ref["i2t"]["R@1"], ref["i2t"]["R@5"], ref["i2t"]["R@10"]]), seed=seed)
     print("wrote", out, "seed", seed, ref["t2i"], ref["i2t"])
 
 
@@ -226,12 +240,12 @@ def rk_e2e_golden(n_img=100, n_cap=500, n_pool=600, gap=RK_E2E_GAP):
     ref = rank_ref.retrieval_metrics_ref(img.astype(np.float32), txt[cap_idx].astype(np.float32), list(cap_ids),
                                          list(range(n_img)))
     out = os.path.join(HERE, "rk_e2e_b32.npz")
-    np.savez_compressed(out, pixel_seed=101, token_seed=102, n_img=n_img, n_pool=n_pool, caption_index=cap_idx,
-                        caption_image_ids=cap_ids, image_features=img.astype(np.float32),
-                        text_features=txt[cap_idx].astype(np.float32), t2i_ranks=ref["t2i_ranks"],
-                        i2t_ranks=ref["i2t_ranks"], gap=gap, min_gap=mg,
-                        t2i=np.array([ref["t2i"][m] for m in ("R@1", "R@5", "R@10", "MRR", "Median_Rank", "Mean_Rank")]),
-                        i2t=np.array([ref["i2t"][m] for m in ("R@1", "R@5", "R@10", "MRR", "Median_Rank", "Mean_Rank")]))
+    save_split(out, pixel_seed=101, token_seed=102, n_img=n_img, n_pool=n_pool, caption_index=cap_idx,
+               caption_image_ids=cap_ids, image_features=img.astype(np.float32),
+               text_features=txt[cap_idx].astype(np.float32), t2i_ranks=ref["t2i_ranks"],
+               i2t_ranks=ref["i2t_ranks"], gap=gap, min_gap=mg,
+               t2i=np.array([ref["t2i"][m] for m in ("R@1", "R@5", "R@10", "MRR", "Median_Rank", "Mean_Rank")]),
+               i2t=np.array([ref["i2t"][m] for m in ("R@1", "R@5", "R@10", "MRR", "Median_Rank", "Mean_Rank")]))
     print("wrote", out, "min decisive gap", mg, ref["t2i"], ref["i2t"])
 
 
