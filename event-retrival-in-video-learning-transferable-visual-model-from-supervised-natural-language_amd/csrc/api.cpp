@@ -15,6 +15,8 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
+#include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <system_error>
@@ -114,49 +116,29 @@ struct Builder {
     if (p) memcpy(img.data() + o, p, n * 4);
     return o;
   }
-  // rows x cols fp32 matrix -> f32 [rows][ldp] (zero padded columns)
-  size_t f32_pad(int64_t rows, int64_t cols, int64_t ldp) {
-    const float* p = take(rows * cols);
-    size_t o = align();
-    img.resize(o + rows * ldp * 4);
-    float* d = (float*)(img.data() + o);
-    for (int64_t r = 0; r < rows; ++r)
-      for (int64_t c = 0; c < ldp; ++c) d[r * ldp + c] = (p && c < cols) ? p[r * cols + c] : 0.f;
-    return o;
+  // GEMM weights in the context's precision (full: f32 as-is, else bf16): element i of the matrix at d
+  static void put(bool full, char* d, int64_t i, float v) {
+    if (full) ((float*)d)[i] = v;
+    else ((uint16_t*)d)[i] = f2bf_host(v);
   }
-  // [rows][cols] fp32 used as x @ P  ->  f32 P^T [cols][rows]
-  size_t f32_t(int64_t rows, int64_t cols) {
-    const float* p = take(rows * cols);
-    size_t o = align();
-    img.resize(o + rows * cols * 4);
-    float* d = (float*)(img.data() + o);
-    for (int64_t c = 0; c < cols; ++c)
-      for (int64_t r = 0; r < rows; ++r) d[c * rows + r] = p ? p[r * cols + c] : 0.f;
-    return o;
-  }
-  // GEMM weight in the context's precision
+  // rows x cols fp32 matrix -> [rows][ldp] (zero padded columns)
   size_t mat(bool full, int64_t rows, int64_t cols, int64_t ldp) {
-    return full ? f32_pad(rows, cols, ldp) : bf16(rows, cols, ldp);
-  }
-  size_t mat_t(bool full, int64_t rows, int64_t cols) { return full ? f32_t(rows, cols) : bf16_t(rows, cols); }
-  // rows x cols fp32 matrix -> bf16 [rows][ldp] (zero padded columns)
-  size_t bf16(int64_t rows, int64_t cols, int64_t ldp) {
     const float* p = take(rows * cols);
     size_t o = align();
-    img.resize(o + rows * ldp * 2);
-    uint16_t* d = (uint16_t*)(img.data() + o);
+    img.resize(o + rows * ldp * (full ? 4 : 2));
+    char* d = img.data() + o;
     for (int64_t r = 0; r < rows; ++r)
-      for (int64_t c = 0; c < ldp; ++c) d[r * ldp + c] = (p && c < cols) ? f2bf_host(p[r * cols + c]) : 0;
+      for (int64_t c = 0; c < ldp; ++c) put(full, d, r * ldp + c, (p && c < cols) ? p[r * cols + c] : 0.f);
     return o;
   }
-  // [rows][cols] fp32 used as x @ P  ->  bf16 P^T [cols][rows]
-  size_t bf16_t(int64_t rows, int64_t cols) {
+  // [rows][cols] fp32 used as x @ P  ->  P^T [cols][rows]
+  size_t mat_t(bool full, int64_t rows, int64_t cols) {
     const float* p = take(rows * cols);
     size_t o = align();
-    img.resize(o + rows * cols * 2);
-    uint16_t* d = (uint16_t*)(img.data() + o);
+    img.resize(o + rows * cols * (full ? 4 : 2));
+    char* d = img.data() + o;
     for (int64_t c = 0; c < cols; ++c)
-      for (int64_t r = 0; r < rows; ++r) d[c * rows + r] = p ? f2bf_host(p[r * cols + c]) : 0;
+      for (int64_t r = 0; r < rows; ++r) put(full, d, c * rows + r, p ? p[r * cols + c] : 0.f);
     return o;
   }
 };
@@ -280,6 +262,7 @@ struct mi_clip {
   char* ws = nullptr;
   float* x = nullptr;
   uint16_t *h = nullptr, *qkv = nullptr, *att = nullptr, *mlp = nullptr, *patches = nullptr, *cls_ln = nullptr;
+  size_t h_bytes = 0, qkv_bytes = 0;   // as reserved: the towers borrow both while they are dead (Carve)
   uint16_t* delta = nullptr;  // bf16 GEMM output added to x by the next residual_ln
   float* rs = nullptr;        // LayerNorm-folded tower: per-row (rstd, rstd * mean), 256 rows of padding
   float* y = nullptr;
@@ -312,7 +295,32 @@ static hipError_t ws_release(mi_clip* c, hipStream_t s) {
   return hipEventRecord(c->ws_evt, s);
 }
 
-static int f32_gemm_mode();
+// A/B switches (MICLIP_* environment overrides of the measured defaults): the A/B build
+// (scripts/ab, MICLIP_AB=1) reads them on every call, so that a test can switch them within one
+// process; the product library always runs the defaults.
+static int ab_int(const char* name, int dflt) {
+#if MICLIP_AB
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+#else
+  (void)name;
+  return dflt;
+#endif
+}
+
+// The fp32 tower's GEMMs (run_tower_f32): 3 = split-f16 operands on the f16 MFMA (the
+// default since round 5, K' = 3K), 6 = split-bf16 operands (round 4, K' = 6K), 0 = the exact-f32
+// MFMA GEMM (precise.hip gemm_f32).  MICLIP_F32_SPLIT selects one in the A/B build (read when a
+// context is created: the weight copies are built for the mode).
+static int f32_gemm_mode() {
+  const int v = ab_int("MICLIP_F32_SPLIT", 3);
+  return v == 0 || v == 6 ? v : 3;
+}
+
+// mi_clip_create owns the half-built context through this: a failed create destroys what it built
+struct CtxDelete {
+  void operator()(mi_clip* c) const { (void)mi_clip_destroy(c); }
+};
 
 extern "C" {
 
@@ -361,7 +369,8 @@ int mi_clip_create(const mi_clip_arch* arch, const float* weights, int64_t numel
                                    (long long)expect);
   HIP_TRY(hipSetDevice(device));
 
-  auto* c = new mi_clip();
+  std::unique_ptr<mi_clip, CtxDelete> own(new mi_clip());
+  mi_clip* c = own.get();
   c->a = a;
   c->device = device;
   c->G = G;
@@ -390,11 +399,9 @@ int mi_clip_create(const mi_clip_arch* arch, const float* weights, int64_t numel
   const size_t o_lnf_g = b.f32(TW), o_lnf_b = b.f32(TW);
   const size_t o_tproj = b.mat_t(full, TW, E);
   const float* ls = b.take(1);
-  if (!b.ok || b.pos != numel || !ls) {
-    delete c;
+  if (!b.ok || b.pos != numel || !ls)
     return fail(MI_ERR_ARG, "weight blob layout mismatch (consumed %lld of %lld)", (long long)b.pos,
                 (long long)numel);
-  }
   // bf16 vision tower: the LayerNorm-folded GEMM weights (run_tower_fold); W % 256 == 0 so
   // that all four GEMMs take the 8-phase kernel
   // (all layers or none: a product W * gamma outside fp16's range, or a non-finite column sum,
@@ -413,11 +420,7 @@ int mi_clip_create(const mi_clip_arch* arch, const float* weights, int64_t numel
   }
   hipError_t e = hipMalloc(&c->wdev, b.img.size());
   if (e == hipSuccess) e = hipMemcpy(c->wdev, b.img.data(), b.img.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (c->wdev) (void)hipFree(c->wdev);
-    delete c;
-    return fail(MI_ERR_HIP, "weight upload: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(MI_ERR_HIP, "weight upload: %s", hipGetErrorString(e));
   char* d = c->wdev;
   auto F = [&](size_t o) { return (const float*)(d + o); };
   auto H = [&](size_t o) { return (const uint16_t*)(d + o); };
@@ -448,31 +451,23 @@ int mi_clip_create(const mi_clip_arch* arch, const float* weights, int64_t numel
         L[i].f_out = F(o.w_out);
         L[i].f_fc = F(o.w_fc);
         L[i].f_proj = F(o.w_proj);
-        {   // EPI_SPLIT_GELU's bound constants, from the host blob (rounded up to stay bounds)
-          const int64_t Wd = (int64_t)(&lo == &vlo ? a.vision_width : a.text_width);
-          const float* wfc = b.src + o.p_w_fc;
-          const float* bfc = b.src + o.p_b_fc;
+        // the split epilogues' bound constants over rows [n0, n1) of a weight and its bias, from the
+        // host blob (rounded up to stay bounds): c_fc (EPI_SPLIT_GELU) and V (rows 2W .. 3W of in_proj)
+        const int64_t Wd = (int64_t)(&lo == &vlo ? a.vision_width : a.text_width);
+        auto bounds = [&](int64_t p_w, int64_t p_b, int64_t n0, int64_t n1, float* bw_out, float* bb_out) {
+          const float *w = b.src + p_w, *bias = b.src + p_b;
           double bw = 0, bb = 0;
-          for (int64_t n = 0; n < 4 * Wd; ++n) {
+          for (int64_t n = n0; n < n1; ++n) {
             double r = 0;
-            for (int64_t k = 0; k < Wd; ++k) r += std::fabs((double)wfc[n * Wd + k]);
+            for (int64_t k = 0; k < Wd; ++k) r += std::fabs((double)w[n * Wd + k]);
             bw = r > bw ? r : bw;
-            bb = std::fabs((double)bfc[n]) > bb ? std::fabs((double)bfc[n]) : bb;
+            bb = std::fabs((double)bias[n]) > bb ? std::fabs((double)bias[n]) : bb;
           }
-          L[i].fc_bw = (float)(bw * (1.0 + 1e-6));
-          L[i].fc_bb = (float)(bb * (1.0 + 1e-6));
-          const float* wq = b.src + o.p_w_qkv;
-          const float* bq = b.src + o.p_b_qkv;
-          bw = bb = 0;
-          for (int64_t n = 2 * Wd; n < 3 * Wd; ++n) {
-            double r = 0;
-            for (int64_t k = 0; k < Wd; ++k) r += std::fabs((double)wq[n * Wd + k]);
-            bw = r > bw ? r : bw;
-            bb = std::fabs((double)bq[n]) > bb ? std::fabs((double)bq[n]) : bb;
-          }
-          L[i].v_bw = (float)(bw * (1.0 + 1e-6));
-          L[i].v_bb = (float)(bb * (1.0 + 1e-6));
-        }
+          *bw_out = (float)(bw * (1.0 + 1e-6));
+          *bb_out = (float)(bb * (1.0 + 1e-6));
+        };
+        bounds(o.p_w_fc, o.p_b_fc, 0, 4 * Wd, &L[i].fc_bw, &L[i].fc_bb);
+        bounds(o.p_w_qkv, o.p_b_qkv, 2 * Wd, 3 * Wd, &L[i].v_bw, &L[i].v_bb);
       } else {
         L[i] = Layer{F(o.ln1_g), F(o.ln1_b), F(o.b_qkv), F(o.b_out), F(o.ln2_g), F(o.ln2_b), F(o.b_fc), F(o.b_proj),
                      H(o.w_qkv), H(o.w_out), H(o.w_fc), H(o.w_proj)};
@@ -574,11 +569,7 @@ int mi_clip_create(const mi_clip_arch* arch, const float* weights, int64_t numel
     const int64_t Wv = a.vision_width;
     const int64_t per_layer = 12 * Wv * Wv + 4 * (12 * Wv * Wv / 64) + 4 * 256;
     e = hipMalloc(&c->wq, per_layer * c->vl.size() + 256);
-    if (e != hipSuccess) {
-      (void)hipFree(c->wdev);
-      delete c;
-      return fail(MI_ERR_HIP, "fp8 weight allocation: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(MI_ERR_HIP, "fp8 weight allocation: %s", hipGetErrorString(e));
     size_t off = 0;
     auto carve = [&](size_t bytes) { char* p = c->wq + off; off += (bytes + 255) & ~(size_t)255; return (uint8_t*)p; };
     for (Layer& L : c->vl) {
@@ -594,15 +585,10 @@ int mi_clip_create(const mi_clip_arch* arch, const float* weights, int64_t numel
       }
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-      (void)hipFree(c->wq);
-      (void)hipFree(c->wdev);
-      delete c;
-      return fail(MI_ERR_HIP, "fp8 weight quantisation: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(MI_ERR_HIP, "fp8 weight quantisation: %s", hipGetErrorString(e));
     c->fp8 = true;
   }
-  *out = c;
+  *out = own.release();
   return MI_OK;
 }
 
@@ -674,6 +660,8 @@ static int reserve_locked(mi_clip* c, int64_t ic, int64_t tc) {
   c->x = (float*)(ws + o_x);
   c->h = (uint16_t*)(ws + o_h);
   c->qkv = (uint16_t*)(ws + o_qkv);
+  c->h_bytes = (size_t)xw * es;
+  c->qkv_bytes = 3 * (size_t)xw * es;
   c->att = (uint16_t*)(ws + o_att);
   c->delta = (uint16_t*)(ws + o_delta);
   c->mlp = (uint16_t*)(ws + o_mlp);
@@ -703,40 +691,16 @@ int mi_clip_reserve(mi_clip* c, int64_t image_chunk, int64_t text_chunk) {
   return reserve_locked(c, image_chunk, text_chunk);
 }
 
-// A/B switches (MICLIP_* environment overrides of the measured defaults) are
-// read only by the A/B build (scripts/ab, MICLIP_AB=1); the product library
-// always runs the defaults.
-static const char* ab_getenv(const char* name) {
-#if MICLIP_AB
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
-
 // GEMM main-loop schedule (gemm.hip): MICLIP_GEMM_VARIANT overrides the default.
-static int gemm_variant() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = ab_getenv("MICLIP_GEMM_VARIANT");
-    v = e ? atoi(e) : 0;
-  }
-  return v;
-}
+static int gemm_variant() { return ab_int("MICLIP_GEMM_VARIANT", 0); }
 
 // Per-GEMM schedule overrides for A/B runs of the whole encoder
 // (MICLIP_GEMM_VARIANT_{QKV,OUT,FC,PROJ}; 0 = MICLIP_GEMM_VARIANT / default).
 enum { GV_QKV = 0, GV_OUT = 1, GV_FC = 2, GV_PROJ = 3 };
 static int gemm_variant_for(int which) {
-  static int v[4] = {-1, -1, -1, -1};
   static const char* names[4] = {"MICLIP_GEMM_VARIANT_QKV", "MICLIP_GEMM_VARIANT_OUT", "MICLIP_GEMM_VARIANT_FC",
                                  "MICLIP_GEMM_VARIANT_PROJ"};
-  if (v[which] < 0) {
-    const char* e = ab_getenv(names[which]);
-    v[which] = e ? atoi(e) : 0;
-  }
-  return v[which];
+  return ab_int(names[which], 0);
 }
 
 static GemmArgs with_variant(GemmArgs g, int which) {
@@ -758,35 +722,14 @@ static GemmArgs gargs(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t
 // Vision residual stream storage: fp16 after the first residual add (2 B
 // instead of 4 per element on each of the 24 residual LayerNorms' read and
 // write); MICLIP_RESID16=0 keeps it f32 (A/B, parity comparisons).
-static int resid16() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = ab_getenv("MICLIP_RESID16");
-    v = e ? atoi(e) != 0 : 1;
-  }
-  return v;
-}
+static int resid16() { return ab_int("MICLIP_RESID16", 1) != 0; }
 // Patch embedding reads the bf16 pixels straight from the GEMM's A-operand DMA
 // (B/32: one 32-pixel row segment per k stage) instead of through an im2col
 // buffer; MICLIP_PATCH_FUSED=0 keeps the im2col pass (A/B).
-static int patch_fused() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = ab_getenv("MICLIP_PATCH_FUSED");
-    v = e ? atoi(e) != 0 : 1;
-  }
-  return v;
-}
+static int patch_fused() { return ab_int("MICLIP_PATCH_FUSED", 1) != 0; }
 // The first block's ln_1 fused into the vision embedding kernel (bf16 tower);
 // MICLIP_EMBED_LN1=0 keeps the separate LayerNorm pass (A/B).
-static int embed_ln1() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = ab_getenv("MICLIP_EMBED_LN1");
-    v = e ? atoi(e) != 0 : 1;
-  }
-  return v;
-}
+static int embed_ln1() { return ab_int("MICLIP_EMBED_LN1", 1) != 0; }
 // xmode of a layer's first residual_ln: the f32 stream from ln_pre is converted at layer 0
 static int xmode_at(int r16, size_t l) { return r16 ? (l == 0 ? 1 : 2) : 0; }
 
@@ -832,10 +775,7 @@ static int run_tower(mi_clip* c, const std::vector<Layer>& layers, int B, int S,
 // up: configs[2] 16.25 -> 16.32 s per step, profiles/r04_v_config2.json).  With the fused residual
 // it pays at L/14 too: 6566 frames/s against 6160 unfolded and 6107 folded without the fusion
 // (10k frames x 256 queries, profiles/r04_al_l14_fold.log).
-static int lnfold(int W) {
-  const char* e = ab_getenv("MICLIP_LNFOLD");   // read per call (A/B tests switch it within one process)
-  return e ? atoi(e) != 0 : W <= 1024;
-}
+static int lnfold(int W) { return ab_int("MICLIP_LNFOLD", W <= 1024) != 0; }
 
 static GemmArgs ln_args(mi_clip* c, const uint16_t* wf, const float* sv, const float* cv, void* out, int N, int M,
                         int W) {
@@ -853,18 +793,50 @@ static GemmArgs ln_args(mi_clip* c, const uint16_t* wf, const float* sv, const f
 // element) instead of writing delta and residual_stats re-reading it (8 B).  The partials live
 // in the h buffer, which the folded tower does not otherwise use.  MICLIP_RESFUSE=0 keeps the
 // separate residual_stats pass (A/B).
-static int resfuse() {
-  const char* e = ab_getenv("MICLIP_RESFUSE");   // read per call (A/B tests switch it within one process)
-  return e ? atoi(e) != 0 : 1;
+static int resfuse() { return ab_int("MICLIP_RESFUSE", 1) != 0; }
+
+// Bump allocator over a workspace buffer that is dead while it is borrowed (qkv after attention;
+// h in the towers that do not write it): sub-buffers on 256-byte boundaries, checked against the
+// size reserve_locked carved for the buffer.  Every layout below fits for S >= 2; the check
+// records and guards that.
+struct Carve {
+  char* base;
+  size_t cap, off = 0, end = 0;
+  void* take(size_t bytes) {
+    char* p = base + off;
+    end = off + bytes;
+    off = (end + 255) & ~(size_t)255;
+    return p;
+  }
+  int fits(const char* what) const {
+    return end <= cap ? MI_OK : fail(MI_ERR_ARG, "%s: %zu bytes needed, %zu reserved", what, end, cap);
+  }
+};
+struct ClsRows { void* att; uint8_t* sc; float* x; };   // cls_gather's compact rows
+struct RowsOut { char* out; int dtype, l2; };           // where one chunk's embeddings go
+
+// `bytes` of the h buffer: the gathered statistics / scales of the CLS rows, EPI_RES16's partials
+static int borrow_h(mi_clip* c, size_t bytes, float** p) {
+  Carve h{(char*)c->h, c->h_bytes};
+  *p = (float*)h.take(bytes);
+  return h.fits("rows borrowed from the h buffer");
 }
 
-// out_proj / c_proj with the residual add fused: x16 += bf16(A W^T + b), partials into c->h
-static int gemm_residual(mi_clip* c, const uint16_t* A, int64_t lda, const uint16_t* w, const float* b, int M, int W,
-                         int K, hipStream_t s) {
-  GemmArgs g = gargs(A, lda, w, K, b, c->x, 2 * W, M, W, K);
-  g.ps = (float*)c->h;
+// dst[b] = src[b * (src_pitch / bytes of a row)]: bytes_per_row of each of B rows
+static int gather_rows(void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t bytes_per_row, int B,
+                       hipStream_t s) {
+  HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, bytes_per_row, B, hipMemcpyDeviceToDevice, s));
+  return MI_OK;
+}
+
+// out_proj / c_proj with the residual add fused: x16 += bf16(A W^T + b) over M rows of the stream
+// x, partials into the h buffer
+static int gemm_residual(mi_clip* c, const uint16_t* A, int64_t lda, const uint16_t* w, const float* b, float* x, int M,
+                         int W, int K, hipStream_t s) {
+  GemmArgs g = gargs(A, lda, w, K, b, x, 2 * W, M, W, K);
+  MI_TRY(borrow_h(c, (size_t)M * (W / 64) * 8, &g.ps));
   HIP_TRY(gemm_bf16(g, EPI_RES16_BF16, s));
-  HIP_TRY(residual_finalize((const float*)c->h, c->rs, M, W, s));
+  HIP_TRY(residual_finalize(g.ps, c->rs, M, W, s));
   return MI_OK;
 }
 
@@ -876,29 +848,68 @@ static int gemm_residual(mi_clip* c, const uint16_t* A, int64_t lda, const uint1
 // values of the full pass's CLS rows bit for bit (each GEMM row's arithmetic does not depend on
 // the rows beside it).  Needs the 8-phase kernel's 256 rows (B >= 256); the compact rows live in
 // the qkv buffer, dead after attention.  MICLIP_CLS_LAST=0 (A/B) runs the full block.
-static int cls_last() {
-  const char* e = ab_getenv("MICLIP_CLS_LAST");
-  return e ? atoi(e) != 0 : 1;
+static int cls_last() { return ab_int("MICLIP_CLS_LAST", 1) != 0; }
+
+// The decision, one for every tower: the last layer, whole 256-row tiles of CLS rows, and the
+// tower's own precondition `pre`
+static bool cls_rows(bool last_layer, int B, int S, bool pre) {
+  return last_layer && pre && B >= 256 && S > 1 && cls_last();
 }
 
-static int last_block_cls(mi_clip* c, const Layer& L, int B, int S, int W, float** xpost, hipStream_t s) {
-  uint16_t* att_c = c->qkv;                                                  // [B][W] bf16
-  float* x_c = (float*)((char*)c->qkv + (((size_t)B * W * 2 + 255) & ~(size_t)255));   // [B] fp16 row slots
-  HIP_TRY(hipMemcpy2DAsync(att_c, (size_t)W * 2, c->att, (size_t)S * W * 2, (size_t)W * 2, B, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpy2DAsync(x_c, (size_t)W * 4, c->x, (size_t)S * W * 4, (size_t)W * 2, B, hipMemcpyDeviceToDevice, s));
-  GemmArgs o = gargs(att_c, W, L.w_out, W, L.b_out, x_c, 2 * W, B, W, W);
-  o.ps = (float*)c->h;
-  HIP_TRY(gemm_bf16(o, EPI_RES16_BF16, s));
-  HIP_TRY(residual_finalize((const float*)c->h, c->rs, B, W, s));
-  GemmArgs f = gargs((const uint16_t*)x_c, 2 * W, L.lw_fc, W, L.lc_fc, c->mlp, 4 * W, B, 4 * W, W);
-  f.variant = 0;
-  f.a_f16 = 1;
-  f.rs = c->rs;
-  f.colv = L.ls_fc;
+// The compact rows, carved from the qkv buffer in this order: the attention output's CLS rows
+// (att_row bytes each; att == nullptr: room only, the consumer reads them in place), the MX tower's
+// scales of those rows (att_sc: stage-major [W / 128][rows padded to even][2], one gather per
+// 128-k stage) and the residual stream's CLS rows (the first x_bytes of each W-float row slot).
+// ln_post then reads the stream at (*xpost, stride 1).
+static int cls_gather(mi_clip* c, int B, int S, int W, const void* att, size_t att_row, const uint8_t* att_sc,
+                      size_t x_bytes, hipStream_t s, ClsRows* r, float** xpost, int64_t* post_stride) {
+  Carve q{(char*)c->qkv, c->qkv_bytes};
+  r->att = q.take(B * att_row);
+  r->sc = (uint8_t*)q.take(att_sc ? ((size_t)W / 128) * (B + 2) * 2 : 0);
+  r->x = (float*)q.take((size_t)B * W * 4);
+  MI_TRY(q.fits("the last block's CLS rows in the qkv buffer"));
+  if (att) MI_TRY(gather_rows(r->att, att_row, att, S * att_row, att_row, B, s));
+  if (att_sc) {
+    const size_t mp = ((size_t)B * S + 1) & ~(size_t)1, bp = ((size_t)B + 1) & ~(size_t)1;
+    for (int st = 0; st < W / 128; ++st)
+      MI_TRY(gather_rows(r->sc + st * bp * 2, 2, att_sc + st * mp * 2, (size_t)S * 2, 2, B, s));
+  }
+  MI_TRY(gather_rows(r->x, (size_t)W * 4, c->x, (size_t)S * W * 4, x_bytes, B, s));
+  *xpost = r->x;
+  *post_stride = 1;
+  return MI_OK;
+}
+
+// in_proj of the CLS-row last block, which reads attention at the CLS queries only: K and V
+// (columns W .. 3W) for every row, Q (columns 0 .. W) for the CLS rows, read and written with a row
+// stride of S, their statistics / scales (vec, vec_row bytes a row; GemmArgs field `f`) gathered
+// into the h buffer.  The other rows' Q columns keep stale finite values, which reach only their own
+// queries' outputs (a query's scores, softmax and P V use its own Q row alone), never read.
+// mk(n0, N, rows, stride): in_proj's columns [n0, n0 + N) over `rows` rows `stride` rows apart
+// (built on ln_args in the folded tower, on sargs in the fp32 one).
+using InProjArgs = std::function<GemmArgs(int n0, int N, int rows, int64_t stride)>;
+static int in_proj_cls(mi_clip* c, int B, int S, int W, const float* vec, size_t vec_row, const float* GemmArgs::*f,
+                       int epi, hipStream_t s, const InProjArgs& mk) {
+  float* vec_c;
+  MI_TRY(borrow_h(c, B * vec_row, &vec_c));
+  HIP_TRY(gemm_bf16(mk(W, 2 * W, B * S, 1), epi, s));
+  MI_TRY(gather_rows(vec_c, vec_row, vec, S * vec_row, vec_row, B, s));
+  GemmArgs q = mk(0, W, B, S);
+  q.*f = vec_c;
+  HIP_TRY(gemm_bf16(q, epi, s));
+  return MI_OK;
+}
+
+static int last_block_cls(mi_clip* c, const Layer& L, int B, int S, int W, float** xpost, int64_t* post_stride,
+                          hipStream_t s) {
+  ClsRows r;   // att [B][W] bf16, x [B] fp16 row slots
+  MI_TRY(cls_gather(c, B, S, W, c->att, (size_t)W * 2, nullptr, (size_t)W * 2, s, &r, xpost, post_stride));
+  MI_TRY(gemm_residual(c, (const uint16_t*)r.att, W, L.w_out, L.b_out, r.x, B, W, W, s));
+  GemmArgs f = ln_args(c, L.lw_fc, L.ls_fc, L.lc_fc, c->mlp, 4 * W, B, W);
+  f.A = (const uint16_t*)r.x;
   HIP_TRY(gemm_bf16(f, EPI_LN_GELU_BF16, s));
   HIP_TRY(gemm_bf16(with_variant(gargs(c->mlp, 4 * W, L.w_proj, 4 * W, L.b_proj, c->delta, W, B, W, 4 * W), GV_PROJ),
                     EPI_BF16, s));
-  *xpost = x_c;
   return MI_OK;
 }
 
@@ -915,33 +926,20 @@ static int run_tower_fold(mi_clip* c, const std::vector<Layer>& layers, int B, i
   for (size_t l = 0; l < layers.size(); ++l) {
     const Layer& L = layers[l];
     const bool last = l + 1 == layers.size();
-    const bool cls = last && fuse && B >= 256 && S > 1 && cls_last();
-    if (cls) {
-      // the last block reads attention at the CLS queries only: K and V for every row, Q for the
-      // CLS rows (strided A and output rows, their LN statistics gathered); the other rows' Q
-      // columns keep stale finite values, which reach only their own queries' outputs (a query's
-      // scores, softmax and P V use its own Q row alone), never read
-      GemmArgs kv = ln_args(c, L.lw_qkv + (size_t)W * W, L.ls_qkv + W, L.lc_qkv + W, c->qkv + W, 2 * W, M, W);
-      kv.ldo = 3 * W;
-      HIP_TRY(gemm_bf16(kv, EPI_LN_BF16, s));
-      float* rs_c = (float*)c->h;
-      HIP_TRY(hipMemcpy2DAsync(rs_c, 8, c->rs, (size_t)S * 8, 8, B, hipMemcpyDeviceToDevice, s));
-      GemmArgs q = ln_args(c, L.lw_qkv, L.ls_qkv, L.lc_qkv, c->qkv, W, B, W);
-      q.lda = (int64_t)S * 2 * W;
-      q.ldo = (int64_t)S * 3 * W;
-      q.rs = rs_c;
-      HIP_TRY(gemm_bf16(q, EPI_LN_BF16, s));
-    } else {
-      HIP_TRY(gemm_bf16(ln_args(c, L.lw_qkv, L.ls_qkv, L.lc_qkv, c->qkv, 3 * W, M, W), EPI_LN_BF16, s));
-    }
+    const bool cls = cls_rows(last, B, S, fuse);
+    // in_proj's columns [n0, n0 + N) over `rows` rows `stride` rows apart
+    auto in_proj = [&](int n0, int N, int rows, int64_t stride) {
+      GemmArgs g = ln_args(c, L.lw_qkv + (size_t)n0 * W, L.ls_qkv + n0, L.lc_qkv + n0, c->qkv + n0, N, rows, W);
+      g.lda = stride * 2 * W;
+      g.ldo = stride * 3 * W;
+      return g;
+    };
+    if (cls) MI_TRY(in_proj_cls(c, B, S, W, c->rs, 8, &GemmArgs::rs, EPI_LN_BF16, s, in_proj));
+    else HIP_TRY(gemm_bf16(in_proj(0, 3 * W, M, 1), EPI_LN_BF16, s));
     HIP_TRY(attention(c->qkv, c->att, B, S, W, cls ? 0x800 : 0, s));   // (cls: the CLS queries' tile only)
-    if (cls) {
-      MI_TRY(last_block_cls(c, L, B, S, W, xpost, s));
-      *post_stride = 1;
-      break;
-    }
+    if (cls) return last_block_cls(c, L, B, S, W, xpost, post_stride, s);
     if (fuse) {
-      MI_TRY(gemm_residual(c, c->att, W, L.w_out, L.b_out, M, W, W, s));
+      MI_TRY(gemm_residual(c, c->att, W, L.w_out, L.b_out, c->x, M, W, W, s));
     } else {
       HIP_TRY(gemm_bf16(with_variant(gargs(c->att, W, L.w_out, W, L.b_out, c->delta, W, M, W, W), GV_OUT), EPI_BF16, s));
       HIP_TRY(residual_stats(c->x, c->delta, c->rs, M, W, s));
@@ -951,7 +949,7 @@ static int run_tower_fold(mi_clip* c, const std::vector<Layer>& layers, int B, i
     HIP_TRY(gemm_bf16(ln_args(c, L.lw_fc, L.ls_fc, L.lc_fc, c->mlp, 4 * W, M, W), EPI_LN_GELU_BF16, s));
     if (tm) HIP_TRY(hipEventRecord(c->ev[2 * c->ev_n++ + 1], s));
     if (fuse && !last) {
-      MI_TRY(gemm_residual(c, c->mlp, 4 * W, L.w_proj, L.b_proj, M, W, 4 * W, s));
+      MI_TRY(gemm_residual(c, c->mlp, 4 * W, L.w_proj, L.b_proj, c->x, M, W, 4 * W, s));
     } else {
       HIP_TRY(gemm_bf16(with_variant(gargs(c->mlp, 4 * W, L.w_proj, 4 * W, L.b_proj, c->delta, W, M, W, 4 * W), GV_PROJ),
                         EPI_BF16, s));
@@ -990,22 +988,13 @@ static int run_tower_mx(mi_clip* c, const std::vector<Layer>& layers, int B, int
     int Mr = M;
     const uint8_t *aq = c->attq, *aqs = c->attqs;
     float* xr = c->x;
-    if (l + 1 == layers.size() && B >= 256 && S > 1 && W % 128 == 0 && cls_last()) {
-      uint8_t* aq_c = (uint8_t*)c->qkv;                                    // [B][W] e4m3
-      uint8_t* aqs_c = aq_c + (((size_t)B * W + 255) & ~(size_t)255);       // [W / 128][Bp][2]
-      float* x_c = (float*)(aqs_c + ((((size_t)W / 128) * (B + 2) * 2 + 255) & ~(size_t)255));
-      const size_t mp = (size_t)((M + 1) & ~1), bp = (size_t)((B + 1) & ~1);
-      HIP_TRY(hipMemcpy2DAsync(aq_c, W, c->attq, (size_t)S * W, W, B, hipMemcpyDeviceToDevice, s));
-      for (int st = 0; st < W / 128; ++st)
-        HIP_TRY(hipMemcpy2DAsync(aqs_c + st * bp * 2, 2, c->attqs + st * mp * 2, (size_t)S * 2, 2, B,
-                                 hipMemcpyDeviceToDevice, s));
-      HIP_TRY(hipMemcpy2DAsync(x_c, (size_t)W * 4, c->x, (size_t)S * W * 4, (size_t)W * 4, B, hipMemcpyDeviceToDevice, s));
+    if (cls_rows(l + 1 == layers.size(), B, S, W % 128 == 0)) {
+      ClsRows r;   // att [B][W] e4m3, sc [W / 128][Bp][2], x [B][W] f32
+      MI_TRY(cls_gather(c, B, S, W, c->attq, W, c->attqs, (size_t)W * 4, s, &r, xpost, post_stride));
       Mr = B;
-      aq = aq_c;
-      aqs = aqs_c;
-      xr = x_c;
-      *xpost = x_c;
-      *post_stride = 1;
+      aq = (const uint8_t*)r.att;
+      aqs = r.sc;
+      xr = r.x;
     }
     HIP_TRY(gemm_mx(margs(aq, aqs, L.q_out, L.s_out, L.b_out, c->delta, W, Mr, W, W), EPI_BF16, s));
     HIP_TRY(residual_ln(xr, c->delta, W, 1, L.ln2_g, L.ln2_b, c->h, Mr, W, s, c->hq, c->hqs, xmode_at(r16, l)));
@@ -1022,191 +1011,151 @@ static int run_tower_mx(mi_clip* c, const std::vector<Layer>& layers, int B, int
 
 static size_t dtype_size(int dt) { return dt == MI_F32 ? 4 : 2; }
 
-// The fp32 tower's GEMMs (run_tower_f32): 3 = split-f16 operands on the f16 MFMA (the
-// default since round 5, K' = 3K), 6 = split-bf16 operands (round 4, K' = 6K), 0 = the exact-f32
-// MFMA GEMM (precise.hip gemm_f32).  MICLIP_F32_SPLIT selects one in the A/B build (read when a
-// context is created: the weight copies are built for the mode).
-static int f32_gemm_mode() {
-  const char* e = ab_getenv("MICLIP_F32_SPLIT");
-  if (!e) return 3;
-  const int v = atoi(e);
-  return v == 0 || v == 6 ? v : 3;
+// The fp32 tower, split-f16 GEMMs (split2h_rows; the default): one f16 GEMM over K' = 3K per
+// linear layer, a1 w1 + a1 w2 + a2 w1 in f32 with the row / column scales in the epilogue --
+// f32-grade results; ln_1 / ln_2 write the split operand directly (layernorm_split2h), attention's
+// and c_fc's outputs are split by one pass each (c_proj's with QuickGELU applied first)
+static int run_tower_f32_split2h(mi_clip* c, const std::vector<Layer>& layers, int B, int S, int W, int causal,
+                                 hipStream_t s, float** xpost, int64_t* post_stride) {
+  const int M = B * S;
+  float *qkv = (float*)c->qkv, *att = (float*)c->att, *mlp = (float*)c->mlp, *rsc = c->rsc;
+  uint16_t* a3 = c->a6;
+  // The A/B switches of this tower (the product runs the defaults):
+  //   fuse_split  the fused c_fc split (MICLIP_F32_FUSED_SPLIT=0 keeps the f32 pre-activation + split
+  //               pass): c_proj's operand [M][12W] after c_fc's [M][3W] in the workspace
+  //   att_fused   MICLIP_F32_ATTN_FUSED=0: attention's f32 output and the split pass (round 5)
+  //   dmask       the activations' split operand stored once, [x1 | x2] (role 2, row stride 2K), where
+  //               the consumer GEMM is the 8-phase kernel (its A_DUP read gives the logical
+  //               [x1 | x1 | x2]): a third less written by the split passes and by c_fc's split
+  //               epilogue (o_dup), bit-identical.  MICLIP_F32_DUP=0 keeps the full layout everywhere
+  //               (a mask: 1 ln_1's split, 2 attention's, 4 ln_2's, 8 c_fc's output)
+  //   dup_on      ... and MICLIP_F32_8Q=0 with it (the ping-pong kernel reads the full layout)
+  const int dmask_env = ab_int("MICLIP_F32_DUP", 15);
+  const struct {
+    bool fuse_split, att_fused, dup_on;
+    int dmask;
+  } sw = {ab_int("MICLIP_F32_FUSED_SPLIT", 1) != 0, ab_int("MICLIP_F32_ATTN_FUSED", 1) != 0,
+          dmask_env != 0 && ab_int("MICLIP_F32_8Q", 1) != 0, dmask_env};
+  uint16_t* a3o = a3 + (int64_t)M * 3 * W;
+  float* rsc_o = rsc + c->rsc_rows;
+  float* rmax = rsc + 2 * c->rsc_rows;
+  auto sargs = [&](const uint16_t* A, int64_t lda_rows, bool dup, const uint16_t* w3, const float* c3, const float* b,
+                   float* out, int64_t ldo, int rows, int N, int K) {   // lda_rows: row stride in rows of the operand
+    GemmArgs g = gargs(A, lda_rows * (dup ? 2 : 3) * K, w3, 3 * K, b, out, ldo, rows, N, 3 * K);
+    g.a_f16 = 1;
+    g.rsc = rsc;
+    g.csc = c3;
+    g.a_dup = dup ? K : 0;
+    return g;
+  };
+  auto dup_ok = [&](int rows, int N, int K, int64_t lda_rows = 1) {   // the consumer takes the 8-phase kernel
+    if (!sw.dup_on) return false;
+    GemmArgs t = sargs(a3, lda_rows, true, nullptr, nullptr, nullptr, nullptr, N, rows, N, K);
+    return gemm_8q_ok(t) != 0;
+  };
+  for (size_t li = 0; li < layers.size(); ++li) {
+    const Layer& L = layers[li];
+    int Mr = M;   // the rows the block's row-wise part runs on (B for the last block's CLS rows)
+    const bool cls = cls_rows(li + 1 == layers.size(), B, S, xpost && !causal);
+    // ln_1's operand feeds in_proj (every row; in the CLS-row last block K / V for every row and Q
+    // for the CLS rows, read with a row stride of S)
+    const bool d1 = (sw.dmask & 1) && (cls ? dup_ok(M, 2 * W, W) && dup_ok(B, W, W, S) : dup_ok(M, 3 * W, W));
+    // S <= 64: attention writes out_proj's split operand itself (attention_f32_split, its scale
+    // bounded through ln_1's row max; round 6), in place of its f32 output and a split pass
+    const bool fuse_att = S <= 64 && sw.att_fused;
+    HIP_TRY(layernorm_split2h(c->x, W, L.ln1_g, L.ln1_b, M, W, a3, rsc, s, fuse_att ? rmax : nullptr, d1));
+    auto in_proj = [&](int n0, int N, int rows, int64_t stride) {
+      return sargs(a3, stride, d1, L.h3_qkv + (size_t)n0 * 3 * W, L.c3_qkv + n0, L.b_qkv + n0, qkv + n0,
+                   stride * 3 * W, rows, N, W);
+    };
+    if (cls) MI_TRY(in_proj_cls(c, B, S, W, rsc, 4, &GemmArgs::rsc, EPI_F32, s, in_proj));
+    else HIP_TRY(gemm_bf16(in_proj(0, 3 * W, M, 1), EPI_F32, s));
+    // attention, then out_proj's operand: written by attention itself (fuse_att; out_proj reads it in
+    // place, in the CLS-row last block the CLS rows with a row stride of S and their scales
+    // gathered, as the CLS Q GEMM's above) or split from attention's f32 output (of the gathered
+    // CLS rows in that block)
+    bool da = (sw.dmask & 2) && fuse_att && (cls ? dup_ok(B, W, W, S) : dup_ok(M, W, W));
+    if (fuse_att)
+      HIP_TRY(attention_f32_split(qkv, rmax, L.v_bw, L.v_bb, a3, da ? 2 : 0, rsc, B, S, W, causal | (cls ? 0x800 : 0),
+                                  s));
+    else
+      HIP_TRY(attention_f32(qkv, att, B, S, W, causal | (cls ? 0x800 : 0), s));   // (cls: the CLS queries' block)
+    ClsRows r = {att, nullptr, c->x};   // att [B][W] f32 (room only with fuse_att), x [B][W] f32
+    float* rsc_a = rsc;   // the scales of out_proj's operand rows
+    if (cls) {
+      MI_TRY(cls_gather(c, B, S, W, fuse_att ? nullptr : att, (size_t)W * 4, nullptr, (size_t)W * 4, s, &r, xpost,
+                        post_stride));
+      Mr = B;
+      if (fuse_att) {
+        MI_TRY(borrow_h(c, (size_t)B * 4, &rsc_a));
+        MI_TRY(gather_rows(rsc_a, 4, rsc, (size_t)S * 4, 4, B, s));
+      }
+    }
+    float* xr = r.x;
+    if (!fuse_att) {
+      da = (sw.dmask & 2) && dup_ok(Mr, W, W);
+      HIP_TRY(split2h_rows((const float*)r.att, W, Mr, W, da ? 2 : 0, 0, a3, rsc, s));
+    }
+    GemmArgs o = sargs(a3, cls && fuse_att ? S : 1, da, L.h3_out, L.c3_out, L.b_out, xr, W, Mr, W, W);
+    o.rsc = rsc_a;
+    HIP_TRY(gemm_bf16(o, EPI_RESID_F32, s));
+    const bool df = (sw.dmask & 4) && dup_ok(Mr, 4 * W, W);      // ln_2's split -> c_fc
+    const bool dp = (sw.dmask & 8) && dup_ok(Mr, W, 4 * W);      // c_fc's output split -> c_proj
+    HIP_TRY(layernorm_split2h(xr, W, L.ln2_g, L.ln2_b, Mr, W, a3, rsc, s, sw.fuse_split ? rmax : nullptr, df));
+    if (sw.fuse_split) {   // c_fc's epilogue writes c_proj's split operand (EPI_SPLIT_GELU)
+      GemmArgs g = sargs(a3, 1, df, L.h3_fc, L.c3_fc, L.b_fc, nullptr, 0, Mr, 4 * W, W);
+      g.out = a3o;
+      g.ldo = (dp ? 2 : 3) * 4 * W;
+      g.o_dup = dp ? 1 : 0;
+      g.rmax = rmax;
+      g.bnd_w = L.fc_bw;
+      g.bnd_b = L.fc_bb;
+      g.rsc_out = rsc_o;
+      HIP_TRY(gemm_bf16(g, EPI_SPLIT_GELU, s));
+      GemmArgs p = sargs(a3o, 1, dp, L.h3_proj, L.c3_proj, L.b_proj, xr, W, Mr, W, 4 * W);
+      p.rsc = rsc_o;
+      HIP_TRY(gemm_bf16(p, EPI_RESID_F32, s));
+    } else {
+      HIP_TRY(gemm_bf16(sargs(a3, 1, df, L.h3_fc, L.c3_fc, L.b_fc, mlp, 4 * W, Mr, 4 * W, W), EPI_F32, s));   // pre-activation
+      HIP_TRY(split2h_rows(mlp, 4 * W, Mr, 4 * W, dp ? 2 : 0, 1, a3, rsc, s));   // QuickGELU, then split
+      HIP_TRY(gemm_bf16(sargs(a3, 1, dp, L.h3_proj, L.c3_proj, L.b_proj, xr, W, Mr, W, 4 * W), EPI_RESID_F32, s));
+    }
+  }
+  return MI_OK;
 }
 
-// The fp32 tower (weight_dtype MI_F32; kernels in precise.hip).  openai/CLIP
-// ResidualAttentionBlock with every tensor f32, the residual adds in the
-// out_proj / c_proj GEMM epilogues:
-//   h = ln_1(x) ; qkv = h W_qkv^T + b ; att = MHA(qkv) ; x += att W_o^T + b_o
-//   h = ln_2(x) ; m = QuickGELU(h W_fc^T + b_fc) ; x += m W_pr^T + b_pr
-// xpost / post_stride (vision): where ln_post reads the CLS rows (the last block may run on them
-// alone, as run_tower_fold's last_block_cls)
-static int run_tower_f32(mi_clip* c, const std::vector<Layer>& layers, int B, int S, int W, int causal,
-                         hipStream_t s, float** xpost = nullptr, int64_t* post_stride = nullptr) {
+// The fp32 tower, split-bf16 GEMMs (split6_rows; A/B, MICLIP_F32_SPLIT=6): one bf16 GEMM over
+// K' = 6K per linear layer, every product term to 2^-16 relative, f32 accumulation -- f32-grade
+// results at bf16 MFMA rates
+static int run_tower_f32_split6(mi_clip* c, const std::vector<Layer>& layers, int B, int S, int W, int causal,
+                                hipStream_t s) {
   const int M = B * S;
-  if (xpost) {
-    *xpost = c->x;
-    *post_stride = S;
-  }
-  float* h = (float*)c->h;
-  float* qkv = (float*)c->qkv;
-  float* att = (float*)c->att;
-  float* mlp = (float*)c->mlp;
-  if (c->a6 && c->rsc && layers.size() && layers[0].h3_qkv) {
-    // split-f16 GEMMs (split2h_rows): one f16 GEMM over K' = 3K per linear layer, a1 w1 + a1 w2 +
-    // a2 w1 in f32 with the row / column scales in the epilogue -- f32-grade results; ln_1 / ln_2
-    // write the split operand directly (layernorm_split2h), attention's and c_fc's outputs are
-    // split by one pass each (c_proj's with QuickGELU applied first)
-    uint16_t* a3 = c->a6;
-    float* rsc = c->rsc;
-    // the fused c_fc split (the default; MICLIP_F32_FUSED_SPLIT=0 in the A/B build keeps the f32
-    // pre-activation + split pass): c_proj's operand [M][12W] after c_fc's [M][3W] in the workspace
-    const char* fe = ab_getenv("MICLIP_F32_FUSED_SPLIT");
-    const bool fuse_split = !fe || atoi(fe) != 0;
-    uint16_t* a3o = a3 + (int64_t)M * 3 * W;
-    float* rsc_o = rsc + c->rsc_rows;
-    float* rmax = rsc + 2 * c->rsc_rows;
-    int Mr = M;   // the rows the block's row-wise part runs on (B for the last block's CLS rows)
-    // The activations' split operand stored once, [x1 | x2] (role 2, row stride 2K), where the
-    // consumer GEMM is the 8-phase kernel (its A_DUP read gives the logical [x1 | x1 | x2]): a third
-    // less written by the split passes and by c_fc's split epilogue (o_dup), bit-identical.
-    // MICLIP_F32_DUP=0 (A/B) keeps the full layout everywhere.
-    // (MICLIP_F32_DUP=mask in the A/B build: 1 ln_1's split, 2 attention's, 4 ln_2's, 8 c_fc's output)
-    const char* de = ab_getenv("MICLIP_F32_DUP");
-    const char* e8 = ab_getenv("MICLIP_F32_8Q");
-    const int dmask = de ? atoi(de) : 15;
-    // MICLIP_F32_ATTN_FUSED=0 (A/B): attention's f32 output and the split pass (round 5)
-    const char* ae = ab_getenv("MICLIP_F32_ATTN_FUSED");
-    const bool att_fused = !ae || atoi(ae) != 0;
-    const bool dup_on = dmask != 0 && (!e8 || atoi(e8) != 0);
-    auto sargs = [&](const uint16_t* A, int64_t lda_rows, bool dup, const uint16_t* w3, const float* c3, const float* b,
-                     float* out, int64_t ldo, int rows, int N, int K) {   // lda_rows: row stride in rows of the operand
-      GemmArgs g = gargs(A, lda_rows * (dup ? 2 : 3) * K, w3, 3 * K, b, out, ldo, rows, N, 3 * K);
-      g.a_f16 = 1;
-      g.rsc = rsc;
-      g.csc = c3;
-      g.a_dup = dup ? K : 0;
-      return g;
-    };
-    auto dup_ok = [&](int rows, int N, int K, int64_t lda_rows = 1) {   // the consumer takes the 8-phase kernel
-      if (!dup_on) return false;
-      GemmArgs t = sargs(a3, lda_rows, true, nullptr, nullptr, nullptr, nullptr, N, rows, N, K);
-      return gemm_8q_ok(t) != 0;
-    };
-    auto gemm3 = [&](int K, const uint16_t* w3, const float* c3, const float* b, float* out, int N, int epi,
-                     bool dup) -> int {
-      HIP_TRY(gemm_bf16(sargs(a3, 1, dup, w3, c3, b, out, N, Mr, N, K), epi, s));
-      return MI_OK;
-    };
-    for (size_t li = 0; li < layers.size(); ++li) {
-      const Layer& L = layers[li];
-      Mr = M;
-      const bool cls = xpost && li + 1 == layers.size() && !causal && B >= 256 && S > 1 && cls_last();
-      // ln_1's operand feeds in_proj (every row; in the CLS-row last block K / V for every row and Q
-      // for the CLS rows, read with a row stride of S)
-      const bool d1 = (dmask & 1) && (cls ? dup_ok(M, 2 * W, W) && dup_ok(B, W, W, S) : dup_ok(M, 3 * W, W));
-      // S <= 64: attention writes out_proj's split operand itself (attention_f32_split, its scale
-      // bounded through ln_1's row max; round 6), in place of its f32 output and a split pass
-      const bool fuse_att = S <= 64 && att_fused;
-      HIP_TRY(layernorm_split2h(c->x, W, L.ln1_g, L.ln1_b, M, W, a3, rsc, s, fuse_att ? rmax : nullptr, d1));
-      if (cls) {   // K and V for every row, Q for the CLS rows only (as run_tower_fold's last block)
-        GemmArgs kv = sargs(a3, 1, d1, L.h3_qkv + (size_t)W * 3 * W, L.c3_qkv + W, L.b_qkv + W, qkv + W, 3 * W, M, 2 * W, W);
-        HIP_TRY(gemm_bf16(kv, EPI_F32, s));
-        float* rsc_c = (float*)c->h;
-        HIP_TRY(hipMemcpy2DAsync(rsc_c, 4, rsc, (size_t)S * 4, 4, B, hipMemcpyDeviceToDevice, s));
-        GemmArgs q = sargs(a3, S, d1, L.h3_qkv, L.c3_qkv, L.b_qkv, qkv, (int64_t)S * 3 * W, B, W, W);
-        q.rsc = rsc_c;
-        HIP_TRY(gemm_bf16(q, EPI_F32, s));
-      } else {
-        MI_TRY(gemm3(W, L.h3_qkv, L.c3_qkv, L.b_qkv, qkv, 3 * W, EPI_F32, d1));
-      }
-      float* xr = c->x;
-      if (fuse_att) {
-        // out_proj reads the operand in place: the CLS rows with a row stride of S in the CLS-row
-        // last block (their scales gathered, as the CLS Q GEMM's above)
-        const bool da = (dmask & 2) && (cls ? dup_ok(B, W, W, S) : dup_ok(M, W, W));
-        HIP_TRY(attention_f32_split(qkv, rmax, L.v_bw, L.v_bb, a3, da ? 2 : 0, rsc, B, S, W,
-                                    causal | (cls ? 0x800 : 0), s));
-        if (cls) {
-          float* x_c = qkv + (((size_t)B * W + 63) & ~(size_t)63);
-          float* rsc_c = (float*)c->h;
-          HIP_TRY(hipMemcpy2DAsync(x_c, (size_t)W * 4, c->x, (size_t)S * W * 4, (size_t)W * 4, B, hipMemcpyDeviceToDevice, s));
-          HIP_TRY(hipMemcpy2DAsync(rsc_c, 4, rsc, (size_t)S * 4, 4, B, hipMemcpyDeviceToDevice, s));
-          Mr = B;
-          xr = x_c;
-          *xpost = x_c;
-          *post_stride = 1;
-          GemmArgs g = sargs(a3, S, da, L.h3_out, L.c3_out, L.b_out, xr, W, B, W, W);
-          g.rsc = rsc_c;
-          HIP_TRY(gemm_bf16(g, EPI_RESID_F32, s));
-        } else {
-          MI_TRY(gemm3(W, L.h3_out, L.c3_out, L.b_out, xr, W, EPI_RESID_F32, da));
-        }
-      } else {
-      HIP_TRY(attention_f32(qkv, att, B, S, W, causal | (cls ? 0x800 : 0), s));   // (cls: the CLS queries' block)
-      const float* ar = att;
-      if (cls) {
-        // the last block after attention on the CLS rows only (see last_block_cls), gathered into
-        // the qkv buffer (dead after attention)
-        float* att_c = qkv;
-        float* x_c = qkv + (((size_t)B * W + 63) & ~(size_t)63);
-        HIP_TRY(hipMemcpy2DAsync(att_c, (size_t)W * 4, att, (size_t)S * W * 4, (size_t)W * 4, B, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpy2DAsync(x_c, (size_t)W * 4, c->x, (size_t)S * W * 4, (size_t)W * 4, B, hipMemcpyDeviceToDevice, s));
-        Mr = B;
-        xr = x_c;
-        ar = att_c;
-        *xpost = x_c;
-        *post_stride = 1;
-      }
-      const bool da = (dmask & 2) && dup_ok(Mr, W, W);          // attention's split -> out_proj
-      HIP_TRY(split2h_rows(ar, W, Mr, W, da ? 2 : 0, 0, a3, rsc, s));
-      MI_TRY(gemm3(W, L.h3_out, L.c3_out, L.b_out, xr, W, EPI_RESID_F32, da));
-      }
-      const bool df = (dmask & 4) && dup_ok(Mr, 4 * W, W);      // ln_2's split -> c_fc
-      const bool dp = (dmask & 8) && dup_ok(Mr, W, 4 * W);      // c_fc's output split -> c_proj
-      if (fuse_split) {   // c_fc's epilogue writes c_proj's split operand (EPI_SPLIT_GELU)
-        HIP_TRY(layernorm_split2h(xr, W, L.ln2_g, L.ln2_b, Mr, W, a3, rsc, s, rmax, df));
-        GemmArgs g = sargs(a3, 1, df, L.h3_fc, L.c3_fc, L.b_fc, nullptr, 0, Mr, 4 * W, W);
-        g.out = a3o;
-        g.ldo = (dp ? 2 : 3) * 4 * W;
-        g.o_dup = dp ? 1 : 0;
-        g.rmax = rmax;
-        g.bnd_w = L.fc_bw;
-        g.bnd_b = L.fc_bb;
-        g.rsc_out = rsc_o;
-        HIP_TRY(gemm_bf16(g, EPI_SPLIT_GELU, s));
-        GemmArgs p = sargs(a3o, 1, dp, L.h3_proj, L.c3_proj, L.b_proj, xr, W, Mr, W, 4 * W);
-        p.rsc = rsc_o;
-        HIP_TRY(gemm_bf16(p, EPI_RESID_F32, s));
-        continue;
-      }
-      HIP_TRY(layernorm_split2h(xr, W, L.ln2_g, L.ln2_b, Mr, W, a3, rsc, s, nullptr, df));
-      MI_TRY(gemm3(W, L.h3_fc, L.c3_fc, L.b_fc, mlp, 4 * W, EPI_F32, df));   // pre-activation
-      HIP_TRY(split2h_rows(mlp, 4 * W, Mr, 4 * W, dp ? 2 : 0, 1, a3, rsc, s));   // QuickGELU, then split
-      MI_TRY(gemm3(4 * W, L.h3_proj, L.c3_proj, L.b_proj, xr, W, EPI_RESID_F32, dp));
-    }
+  float *h = (float*)c->h, *qkv = (float*)c->qkv, *att = (float*)c->att, *mlp = (float*)c->mlp;
+  uint16_t* a6 = c->a6;
+  auto lin = [&](const float* in, int K, const uint16_t* w6, const float* b, float* out, int N, int epi,
+                 int gelu) -> int {
+    HIP_TRY(split6_rows(in, K, M, K, 0, gelu, a6, s));
+    HIP_TRY(gemm_bf16(gargs(a6, 6 * K, w6, 6 * K, b, out, N, M, N, 6 * K), epi, s));
     return MI_OK;
+  };
+  for (const Layer& L : layers) {
+    HIP_TRY(layernorm_f32(c->x, W, L.ln1_g, L.ln1_b, h, W, M, W, s));
+    MI_TRY(lin(h, W, L.s6_qkv, L.b_qkv, qkv, 3 * W, EPI_F32, 0));
+    HIP_TRY(attention_f32(qkv, att, B, S, W, causal, s));
+    MI_TRY(lin(att, W, L.s6_out, L.b_out, c->x, W, EPI_RESID_F32, 0));
+    HIP_TRY(layernorm_f32(c->x, W, L.ln2_g, L.ln2_b, h, W, M, W, s));
+    MI_TRY(lin(h, W, L.s6_fc, L.b_fc, mlp, 4 * W, EPI_F32, 0));   // pre-activation: the split applies QuickGELU
+    MI_TRY(lin(mlp, 4 * W, L.s6_proj, L.b_proj, c->x, W, EPI_RESID_F32, 1));
   }
-  if (c->a6 && layers.size() && layers[0].s6_qkv) {
-    // split-bf16 GEMMs (split6_rows): one bf16 GEMM over K' = 6K per linear layer, every product
-    // term to 2^-16 relative, f32 accumulation -- f32-grade results at bf16 MFMA rates
-    uint16_t* a6 = c->a6;
-    auto lin = [&](const float* in, int K, const uint16_t* w6, const float* b, float* out, int N, int epi,
-                   int gelu) -> int {
-      HIP_TRY(split6_rows(in, K, M, K, 0, gelu, a6, s));
-      HIP_TRY(gemm_bf16(gargs(a6, 6 * K, w6, 6 * K, b, out, N, M, N, 6 * K), epi, s));
-      return MI_OK;
-    };
-    for (const Layer& L : layers) {
-      HIP_TRY(layernorm_f32(c->x, W, L.ln1_g, L.ln1_b, h, W, M, W, s));
-      MI_TRY(lin(h, W, L.s6_qkv, L.b_qkv, qkv, 3 * W, EPI_F32, 0));
-      HIP_TRY(attention_f32(qkv, att, B, S, W, causal, s));
-      MI_TRY(lin(att, W, L.s6_out, L.b_out, c->x, W, EPI_RESID_F32, 0));
-      HIP_TRY(layernorm_f32(c->x, W, L.ln2_g, L.ln2_b, h, W, M, W, s));
-      MI_TRY(lin(h, W, L.s6_fc, L.b_fc, mlp, 4 * W, EPI_F32, 0));   // pre-activation: the split applies QuickGELU
-      MI_TRY(lin(mlp, 4 * W, L.s6_proj, L.b_proj, c->x, W, EPI_RESID_F32, 1));
-    }
-    return MI_OK;
-  }
+  return MI_OK;
+}
+
+// The fp32 tower on the exact-f32 MFMA GEMM (precise.hip gemm_f32; A/B, MICLIP_F32_SPLIT=0, and
+// the fallback when the split weight copies could not be built)
+static int run_tower_f32_exact(mi_clip* c, const std::vector<Layer>& layers, int B, int S, int W, int causal,
+                               hipStream_t s) {
+  const int M = B * S;
+  float *h = (float*)c->h, *qkv = (float*)c->qkv, *att = (float*)c->att, *mlp = (float*)c->mlp;
   for (const Layer& L : layers) {
     HIP_TRY(layernorm_f32(c->x, W, L.ln1_g, L.ln1_b, h, W, M, W, s));
     HIP_TRY(gemm_f32(h, W, L.f_qkv, W, L.b_qkv, qkv, 3 * W, M, 3 * W, W, EPI_F32, s));
@@ -1219,18 +1168,59 @@ static int run_tower_f32(mi_clip* c, const std::vector<Layer>& layers, int B, in
   return MI_OK;
 }
 
-static int encode_image_f32(mi_clip* c, const char* px, int nb, int in_dtype, char* out, int out_dtype,
-                            int l2_normalize, hipStream_t s) {
+// The fp32 tower (weight_dtype MI_F32; kernels in precise.hip).  openai/CLIP
+// ResidualAttentionBlock with every tensor f32, the residual adds in the
+// out_proj / c_proj GEMM epilogues:
+//   h = ln_1(x) ; qkv = h W_qkv^T + b ; att = MHA(qkv) ; x += att W_o^T + b_o
+//   h = ln_2(x) ; m = QuickGELU(h W_fc^T + b_fc) ; x += m W_pr^T + b_pr
+// on the GEMMs the context's weight copies were built for (f32_gemm_mode).
+// xpost / post_stride (vision): where ln_post reads the CLS rows (the last block may run on them
+// alone, as run_tower_fold's last_block_cls)
+static int run_tower_f32(mi_clip* c, const std::vector<Layer>& layers, int B, int S, int W, int causal,
+                         hipStream_t s, float** xpost = nullptr, int64_t* post_stride = nullptr) {
+  if (xpost) {
+    *xpost = c->x;
+    *post_stride = S;
+  }
+  if (c->a6 && c->rsc && layers.size() && layers[0].h3_qkv)
+    return run_tower_f32_split2h(c, layers, B, S, W, causal, s, xpost, post_stride);
+  if (c->a6 && layers.size() && layers[0].s6_qkv) return run_tower_f32_split6(c, layers, B, S, W, causal, s);
+  return run_tower_f32_exact(c, layers, B, S, W, causal, s);
+}
+
+// The tail of an encode, fp32 tower: the final LayerNorm of the pooled rows (x, row stride ldx;
+// tk != nullptr: the EOT rows of S-token sequences) -> projection GEMM -> the caller's buffer
+static int project_rows_f32(mi_clip* c, const float* x, int64_t ldx, const float* g, const float* b, const float* proj,
+                            int n, int W, const RowsOut& o, hipStream_t s, const int32_t* tk = nullptr, int S = 0) {
+  const int E = c->a.embed_dim;
+  float* cls = (float*)c->cls_ln;
+  HIP_TRY(layernorm_f32(x, ldx, g, b, cls, W, n, W, s, tk, S));
+  HIP_TRY(gemm_f32(cls, W, proj, W, nullptr, c->y, E, n, E, W, EPI_F32, s));
+  HIP_TRY(finalize_rows(c->y, o.out, o.dtype, n, E, o.l2, s));
+  return MI_OK;
+}
+
+// ... bf16 / fp8 towers: the caller's final LayerNorm wrote cls_ln (residual_ln over the CLS rows,
+// eot_gather_ln over the EOT rows)
+static int project_rows(mi_clip* c, const uint16_t* proj_t, int n, int W, const RowsOut& o, hipStream_t s) {
+  const int E = c->a.embed_dim;
+  HIP_TRY(gemm_bf16(gargs(c->cls_ln, W, proj_t, W, nullptr, c->y, E, n, E, W), EPI_F32, s));
+  HIP_TRY(finalize_rows(c->y, o.out, o.dtype, n, E, o.l2, s));
+  return MI_OK;
+}
+
+// One chunk of an encode call, one function per entry point and precision, all of one shape: `n`
+// rows of `in` (pixels of in_dtype / int32 tokens) -> n embeddings at o
+static int image_chunk_f32(mi_clip* c, const void* px, int in_dtype, int nb, const RowsOut& o, hipStream_t s) {
   const mi_clip_arch& a = c->a;
-  const int W = a.vision_width, E = a.embed_dim, S = c->S_v, R = a.image_resolution, P = a.vision_patch_size;
+  const int W = a.vision_width, S = c->S_v, R = a.image_resolution, P = a.vision_patch_size;
   const int G2 = c->G * c->G;
   float* patches = (float*)c->patches;
   // conv1 as a split-f16 GEMM (rows remapped past CLS); its operand straight from the pixels where
   // the patch rows are float4-aligned (P % 4 == 0: B/32, B/16; MICLIP_IM2COL_SPLIT=0 in the A/B
   // build keeps im2col_f32 + split2h_rows)
-  const char* fe = ab_getenv("MICLIP_IM2COL_SPLIT");
-  const bool fused = (!fe || atoi(fe) != 0) && P % 4 == 0 && R % 4 == 0 && c->Kp32 == 3 * P * P && c->Kp32 <= 4096 &&
-                     ((uintptr_t)px & 15) == 0;
+  const bool fused = ab_int("MICLIP_IM2COL_SPLIT", 1) != 0 && P % 4 == 0 && R % 4 == 0 && c->Kp32 == 3 * P * P &&
+                     c->Kp32 <= 4096 && ((uintptr_t)px & 15) == 0;
   const bool split3 = c->conv_h3 && c->a6 && c->rsc;
   if (!(split3 && fused)) HIP_TRY(im2col_f32(px, in_dtype == MI_BF16, patches, nb, R, P, c->Kp32, s));
   if (split3) {
@@ -1252,130 +1242,117 @@ static int encode_image_f32(mi_clip* c, const char* px, int nb, int in_dtype, ch
   HIP_TRY(vision_embed_ln(c->x, c->cls, c->vpos, c->ln_pre_g, c->ln_pre_b, nb, S, W, s));
   float* xpost = c->x;
   int64_t post_stride = S;
-  int r = run_tower_f32(c, c->vl, nb, S, W, 0, s, &xpost, &post_stride);
-  if (r) return r;
-  float* cls = (float*)c->cls_ln;
-  HIP_TRY(layernorm_f32(xpost, post_stride * W, c->ln_post_g, c->ln_post_b, cls, W, nb, W, s));
-  HIP_TRY(gemm_f32(cls, W, c->vproj_f, W, nullptr, c->y, E, nb, E, W, EPI_F32, s));
-  HIP_TRY(finalize_rows(c->y, out, out_dtype, nb, E, l2_normalize, s));
-  return MI_OK;
+  MI_TRY(run_tower_f32(c, c->vl, nb, S, W, 0, s, &xpost, &post_stride));
+  return project_rows_f32(c, xpost, post_stride * W, c->ln_post_g, c->ln_post_b, c->vproj_f, nb, W, o, s);
 }
 
-static int encode_text_f32(mi_clip* c, const int32_t* tk, int nq, char* out, int out_dtype, int l2_normalize,
-                           hipStream_t s) {
+static int text_chunk_f32(mi_clip* c, const void* in, int, int nq, const RowsOut& o, hipStream_t s) {
   const mi_clip_arch& a = c->a;
-  const int W = a.text_width, E = a.embed_dim, S = a.context_length;
+  const int W = a.text_width, S = a.context_length;
+  const int32_t* tk = (const int32_t*)in;
   HIP_TRY(text_embed(tk, c->tok_emb, c->tpos, c->x, nq, S, W, a.vocab_size, s));
-  int r = run_tower_f32(c, c->tl, nq, S, W, 1, s);
-  if (r) return r;
-  float* cls = (float*)c->cls_ln;
-  HIP_TRY(layernorm_f32(c->x, W, c->lnf_g, c->lnf_b, cls, W, nq, W, s, tk, S));
-  HIP_TRY(gemm_f32(cls, W, c->tproj_f, W, nullptr, c->y, E, nq, E, W, EPI_F32, s));
-  HIP_TRY(finalize_rows(c->y, out, out_dtype, nq, E, l2_normalize, s));
+  MI_TRY(run_tower_f32(c, c->tl, nq, S, W, 1, s));
+  return project_rows_f32(c, c->x, W, c->lnf_g, c->lnf_b, c->tproj_f, nq, W, o, s, tk, S);
+}
+
+static int image_chunk(mi_clip* c, const void* px, int in_dtype, int nb, const RowsOut& o, hipStream_t s) {
+  const mi_clip_arch& a = c->a;
+  const int W = a.vision_width, S = c->S_v, R = a.image_resolution, P = a.vision_patch_size;
+  const int G2 = c->G * c->G;
+  const bool fused = patch_fused() && in_dtype == MI_BF16 && P == 32 && c->Kp == 3 * P * P && R % 8 == 0 &&
+                     ((uintptr_t)px & 15) == 0 && (int64_t)nb * G2 >= 1024;
+  GemmArgs pg;
+  if (fused) {
+    pg = gargs((const uint16_t*)px, 0, c->conv_w, c->Kp, nullptr, c->x, W, nb * G2, W, c->Kp);
+    pg.patch_R = R;
+  } else {
+    HIP_TRY(im2col(px, in_dtype == MI_BF16, c->patches, nb, R, P, c->Kp, s));
+    pg = gargs(c->patches, c->Kp, c->conv_w, c->Kp, nullptr, c->x, W, nb * G2, W, c->Kp);
+  }
+  pg.group = G2;
+  pg.gstride = S;
+  pg.goffset = 1;
+  HIP_TRY(gemm_bf16(pg, EPI_F32, s));
+  // LayerNorm-folded tower: bf16 weights folded at create (W % 256 == 0), whole 256-row tiles
+  const bool fold = !c->fp8 && !c->vl.empty() && c->vl[0].lw_qkv && lnfold(W) && (int64_t)nb * S >= 256;
+  const int r16 = fold || (resid16() && !c->vl.empty());   // the residual stream is fp16 on return
+  float* xpost = c->x;
+  int64_t post_stride = S;
+  if (fold) {
+    HIP_TRY(vision_embed_ln16(c->x, c->cls, c->vpos, c->ln_pre_g, c->ln_pre_b, nb, S, W, c->rs, s));
+    MI_TRY(run_tower_fold(c, c->vl, nb, S, W, s, &xpost, &post_stride));
+  } else {
+    const bool fuse_ln1 = !c->fp8 && !c->vl.empty() && embed_ln1();  // the MX tower's first LN writes fp8 itself
+    HIP_TRY(vision_embed_ln(c->x, c->cls, c->vpos, c->ln_pre_g, c->ln_pre_b, nb, S, W, s,
+                            fuse_ln1 ? c->vl[0].ln1_g : nullptr, fuse_ln1 ? c->vl[0].ln1_b : nullptr,
+                            fuse_ln1 ? c->h : nullptr));
+    MI_TRY(c->fp8 ? run_tower_mx(c, c->vl, nb, S, W, s, r16, &xpost, &post_stride)
+                  : run_tower(c, c->vl, nb, S, W, 0, s, r16, fuse_ln1));
+  }
+  // ln_post(x[:, 0] + last c_proj delta) over the CLS rows only
+  HIP_TRY(residual_ln(xpost, c->delta, post_stride * W, 0, c->ln_post_g, c->ln_post_b, c->cls_ln, nb, W, s, nullptr,
+                      nullptr, r16 ? 2 : 0));
+  return project_rows(c, c->vproj_t, nb, W, o, s);
+}
+
+static int text_chunk(mi_clip* c, const void* in, int, int nq, const RowsOut& o, hipStream_t s) {
+  const mi_clip_arch& a = c->a;
+  const int W = a.text_width, S = a.context_length;
+  const int32_t* tk = (const int32_t*)in;
+  HIP_TRY(text_embed(tk, c->tok_emb, c->tpos, c->x, nq, S, W, a.vocab_size, s));
+  MI_TRY(run_tower(c, c->tl, nq, S, W, 1, s));
+  HIP_TRY(eot_gather_ln(tk, c->x, c->delta, c->lnf_g, c->lnf_b, c->cls_ln, nq, S, W, s));
+  return project_rows(c, c->tproj_t, nq, W, o, s);
+}
+
+// Once ws_acquire has succeeded the workspace event is recorded on every return: after a failed
+// launch in the middle of an encode, a call on another stream still waits for the kernels already
+// queued on the workspace.  The success path reports the record's own error (release()).
+struct WsGuard {
+  mi_clip* c;
+  hipStream_t s;
+  bool armed = true;
+  ~WsGuard() { if (armed) (void)ws_release(c, s); }
+  hipError_t release() { armed = false; return ws_release(c, s); }
+};
+
+// What the two encoders share: argument checks, the lock, the lazy reserve, the device, the
+// workspace ordering and the chunk loop (image: `in` is pixels of in_dtype, else int32 tokens)
+static int encode(mi_clip* c, const char* who, bool image, const void* in, int in_dtype, int64_t n, void* out,
+                  int out_dtype, int l2_normalize, void* stream) {
+  if (!c || (!in && n > 0) || (!out && n > 0) || n < 0) return fail(MI_ERR_ARG, "%s: bad arguments", who);
+  if (image && in_dtype != MI_F32 && in_dtype != MI_BF16) return fail(MI_ERR_ARG, "%s: in_dtype must be f32/bf16", who);
+  if (out_dtype < MI_F32 || out_dtype > MI_F16) return fail(MI_ERR_ARG, "%s: bad out_dtype", who);
+  if (l2_normalize < 0 || l2_normalize > 2) return fail(MI_ERR_ARG, "%s: l2_normalize must be 0, 1 or 2", who);
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->ws) MI_TRY(reserve_locked(c, 256, 64));
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(ws_acquire(c, s));
+  WsGuard ws{c, s};
+  const mi_clip_arch& a = c->a;
+  const int64_t step = image ? c->img_chunk : c->txt_chunk;
+  const size_t in_row = image ? (size_t)3 * a.image_resolution * a.image_resolution * dtype_size(in_dtype)
+                              : (size_t)a.context_length * sizeof(int32_t);
+  const size_t out_row = (size_t)a.embed_dim * dtype_size(out_dtype);
+  const auto chunk = image ? (c->f32 ? image_chunk_f32 : image_chunk) : (c->f32 ? text_chunk_f32 : text_chunk);
+  for (int64_t c0 = 0; c0 < n; c0 += step) {
+    const int nb = (int)std::min(n - c0, step);
+    MI_TRY(chunk(c, (const char*)in + c0 * in_row, in_dtype, nb, RowsOut{(char*)out + c0 * out_row, out_dtype, l2_normalize},
+                 s));
+  }
+  HIP_TRY(ws.release());
   return MI_OK;
 }
 
 int mi_clip_encode_image(mi_clip* c, const void* pixels, int64_t B, int in_dtype, void* out, int out_dtype,
                          int l2_normalize, void* stream) {
-  if (!c || (!pixels && B > 0) || (!out && B > 0) || B < 0) return fail(MI_ERR_ARG, "encode_image: bad arguments");
-  if (in_dtype != MI_F32 && in_dtype != MI_BF16) return fail(MI_ERR_ARG, "encode_image: in_dtype must be f32/bf16");
-  if (out_dtype < MI_F32 || out_dtype > MI_F16) return fail(MI_ERR_ARG, "encode_image: bad out_dtype");
-  if (l2_normalize < 0 || l2_normalize > 2) return fail(MI_ERR_ARG, "encode_image: l2_normalize must be 0, 1 or 2");
-  std::lock_guard<std::mutex> g(c->mu);
-  if (!c->ws) {
-    int r = reserve_locked(c, 256, 64);
-    if (r) return r;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(ws_acquire(c, s));
-  const mi_clip_arch& a = c->a;
-  const int W = a.vision_width, E = a.embed_dim, S = c->S_v, R = a.image_resolution, P = a.vision_patch_size;
-  const int G2 = c->G * c->G;
-  const size_t in_img = (size_t)3 * R * R * dtype_size(in_dtype);
-  for (int64_t c0 = 0; c0 < B; c0 += c->img_chunk) {
-    const int nb = (int)((B - c0) < c->img_chunk ? (B - c0) : c->img_chunk);
-    const char* px = (const char*)pixels + c0 * in_img;
-    if (c->f32) {
-      int r = encode_image_f32(c, px, nb, in_dtype, (char*)out + c0 * E * dtype_size(out_dtype), out_dtype,
-                               l2_normalize, s);
-      if (r) return r;
-      continue;
-    }
-    const bool fused = patch_fused() && in_dtype == MI_BF16 && P == 32 && c->Kp == 3 * P * P && R % 8 == 0 &&
-                       ((uintptr_t)px & 15) == 0 && (int64_t)nb * G2 >= 1024;
-    GemmArgs pg;
-    if (fused) {
-      pg = gargs((const uint16_t*)px, 0, c->conv_w, c->Kp, nullptr, c->x, W, nb * G2, W, c->Kp);
-      pg.patch_R = R;
-    } else {
-      HIP_TRY(im2col(px, in_dtype == MI_BF16, c->patches, nb, R, P, c->Kp, s));
-      pg = gargs(c->patches, c->Kp, c->conv_w, c->Kp, nullptr, c->x, W, nb * G2, W, c->Kp);
-    }
-    pg.group = G2;
-    pg.gstride = S;
-    pg.goffset = 1;
-    HIP_TRY(gemm_bf16(pg, EPI_F32, s));
-    // LayerNorm-folded tower: bf16 weights folded at create (W % 256 == 0), whole 256-row tiles
-    const bool fold = !c->fp8 && !c->vl.empty() && c->vl[0].lw_qkv && lnfold(W) && (int64_t)nb * S >= 256;
-    int r;
-    float* xpost = c->x;
-    int64_t post_stride = S;
-    if (fold) {
-      HIP_TRY(vision_embed_ln16(c->x, c->cls, c->vpos, c->ln_pre_g, c->ln_pre_b, nb, S, W, c->rs, s));
-      r = run_tower_fold(c, c->vl, nb, S, W, s, &xpost, &post_stride);
-    } else {
-      const bool fuse_ln1 = !c->fp8 && !c->vl.empty() && embed_ln1();  // the MX tower's first LN writes fp8 itself
-      HIP_TRY(vision_embed_ln(c->x, c->cls, c->vpos, c->ln_pre_g, c->ln_pre_b, nb, S, W, s,
-                              fuse_ln1 ? c->vl[0].ln1_g : nullptr, fuse_ln1 ? c->vl[0].ln1_b : nullptr,
-                              fuse_ln1 ? c->h : nullptr));
-      r = c->fp8 ? run_tower_mx(c, c->vl, nb, S, W, s, resid16() && !c->vl.empty(), &xpost, &post_stride)
-                 : run_tower(c, c->vl, nb, S, W, 0, s, resid16() && !c->vl.empty(), fuse_ln1);
-    }
-    if (r) return r;
-    const int r16 = fold || (resid16() && !c->vl.empty());
-    // ln_post(x[:, 0] + last c_proj delta) over the CLS rows only
-    HIP_TRY(residual_ln(xpost, c->delta, post_stride * W, 0, c->ln_post_g, c->ln_post_b, c->cls_ln, nb, W, s, nullptr,
-                        nullptr, r16 ? 2 : 0));
-    HIP_TRY(gemm_bf16(gargs(c->cls_ln, W, c->vproj_t, W, nullptr, c->y, E, nb, E, W), EPI_F32, s));
-    HIP_TRY(finalize_rows(c->y, (char*)out + c0 * E * dtype_size(out_dtype), out_dtype, nb, E, l2_normalize, s));
-  }
-  HIP_TRY(ws_release(c, s));
-  return MI_OK;
+  return encode(c, "encode_image", true, pixels, in_dtype, B, out, out_dtype, l2_normalize, stream);
 }
 
 int mi_clip_encode_text(mi_clip* c, const int32_t* tokens, int64_t Q, void* out, int out_dtype, int l2_normalize,
                         void* stream) {
-  if (!c || (!tokens && Q > 0) || (!out && Q > 0) || Q < 0) return fail(MI_ERR_ARG, "encode_text: bad arguments");
-  if (out_dtype < MI_F32 || out_dtype > MI_F16) return fail(MI_ERR_ARG, "encode_text: bad out_dtype");
-  if (l2_normalize < 0 || l2_normalize > 2) return fail(MI_ERR_ARG, "encode_text: l2_normalize must be 0, 1 or 2");
-  std::lock_guard<std::mutex> g(c->mu);
-  if (!c->ws) {
-    int r = reserve_locked(c, 256, 64);
-    if (r) return r;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(ws_acquire(c, s));
-  const mi_clip_arch& a = c->a;
-  const int W = a.text_width, E = a.embed_dim, S = a.context_length;
-  for (int64_t c0 = 0; c0 < Q; c0 += c->txt_chunk) {
-    const int nq = (int)((Q - c0) < c->txt_chunk ? (Q - c0) : c->txt_chunk);
-    const int32_t* tk = tokens + c0 * S;
-    if (c->f32) {
-      int r = encode_text_f32(c, tk, nq, (char*)out + c0 * E * dtype_size(out_dtype), out_dtype, l2_normalize, s);
-      if (r) return r;
-      continue;
-    }
-    HIP_TRY(text_embed(tk, c->tok_emb, c->tpos, c->x, nq, S, W, a.vocab_size, s));
-    int r = run_tower(c, c->tl, nq, S, W, 1, s);
-    if (r) return r;
-    HIP_TRY(eot_gather_ln(tk, c->x, c->delta, c->lnf_g, c->lnf_b, c->cls_ln, nq, S, W, s));
-    HIP_TRY(gemm_bf16(gargs(c->cls_ln, W, c->tproj_t, W, nullptr, c->y, E, nq, E, W), EPI_F32, s));
-    HIP_TRY(finalize_rows(c->y, (char*)out + c0 * E * dtype_size(out_dtype), out_dtype, nq, E, l2_normalize, s));
-  }
-  HIP_TRY(ws_release(c, s));
-  return MI_OK;
+  return encode(c, "encode_text", false, tokens, 0, Q, out, out_dtype, l2_normalize, stream);
 }
 
 size_t mi_rank_workspace_bytes(int64_t N, int64_t Q, int32_t k) {
