@@ -1394,6 +1394,44 @@ int mi_rank_topk(const void* corpus, int64_t N, int64_t D, int corpus_dtype, con
   return MI_OK;
 }
 
+static int check_filtered_k(int32_t k) {
+  if (k < 1 || k > RANK_REG_K) return fail(MI_ERR_UNSUPPORTED, "k must be in [1, %d] (got %d)", RANK_REG_K, k);
+  return MI_OK;
+}
+
+size_t mi_rank_filtered_workspace_bytes(int64_t N, int64_t Q, int32_t k) {
+  if (N < 0 || Q < 0 || k < 1 || k > RANK_REG_K) return 0;
+  return rank_filtered_workspace_bytes(N, Q, k);
+}
+
+int mi_rank_topk_filtered(const void* corpus, int64_t N, int64_t D, int corpus_dtype, const float* queries, int64_t Q,
+                          int32_t k, int64_t index_base, int norm_mode, int nan_policy, const uint32_t* row_mask,
+                          const int64_t* query_range, float* out_scores, int64_t* out_index, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  int r = check_filtered_k(k);
+  if (r) return r;
+  r = check_rank_args(N, D, corpus_dtype, Q, k, norm_mode, nan_policy);
+  if (r) return r;
+  if (N > rank_filtered_max_rows(k))
+    return fail(MI_ERR_UNSUPPORTED, "mi_rank_topk_filtered: N > %lld per call: shard the corpus",
+                (long long)rank_filtered_max_rows(k));
+  if (Q == 0) return MI_OK;
+  const size_t need = N > 0 ? rank_filtered_workspace_bytes(N, Q, k) : 0;
+  if (need && (!workspace || workspace_bytes < need))
+    return fail(MI_ERR_ARG, "mi_rank_topk_filtered: workspace too small (%zu < %zu)", workspace_bytes, need);
+  if (!queries || !out_scores || !out_index || (N > 0 && !corpus))
+    return fail(MI_ERR_ARG, "mi_rank_topk_filtered: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int nf = nan_policy == MI_NAN_FIRST;
+  if (N == 0) {
+    HIP_TRY(rank_fill_empty(Q, k, out_scores, out_index, s));
+    return MI_OK;
+  }
+  HIP_TRY(rank_topk_filtered(corpus, N, D, corpus_dtype, queries, Q, k, index_base, norm_mode, nf, row_mask,
+                             query_range, out_scores, out_index, workspace, s));
+  return MI_OK;
+}
+
 int mi_mirror_build(const void* corpus, int64_t N, int64_t D, int corpus_dtype, void* mirror, void* stream) {
   int r = check_rank_args(N, D, corpus_dtype, 1, 1, MI_NORM_L2, MI_NAN_FIRST);
   if (r) return r;

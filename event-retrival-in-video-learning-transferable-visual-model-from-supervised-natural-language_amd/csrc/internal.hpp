@@ -252,6 +252,13 @@ hipError_t score_matrix(const void* corpus, int64_t N, int64_t D, int dt, const 
                         float* out, hipStream_t s);
 hipError_t rank_of_targets(const float* S, int64_t Q, int64_t N, const int64_t* pq, const int64_t* pt, int64_t T,
                            int64_t* out, hipStream_t s);
+// filtered ranking (rank_filter.hip): a row bitmask and / or per-query row ranges (device, nullable),
+// 1 <= k <= RANK_REG_K, 1 <= N <= rank_filtered_max_rows(k)
+size_t rank_filtered_workspace_bytes(int64_t N, int64_t Q, int k);
+int64_t rank_filtered_max_rows(int k);
+hipError_t rank_topk_filtered(const void* corpus, int64_t N, int64_t D, int dt, const float* q, int64_t Q, int k,
+                              int64_t base, int norm_mode, int nan_first, const uint32_t* row_mask,
+                              const int64_t* query_range, float* out_s, int64_t* out_i, void* ws, hipStream_t s);
 // mirrored corpus (rank_mirror.hip): fp16 unit-row mirror + certified exact re-score, k <= 16
 constexpr int MIRROR_MAX_K = 16;
 int rank_mirror_supported(int64_t D);

@@ -43,6 +43,7 @@ EXPORTS = (
     "mi_jpeg_decode_transform", "mi_op_split2h", "mi_op_gemm_split2h", "mi_op_attention_f32",
     "mi_op_attention_f32_split",
     "mi_clip_kernel_events", "mi_clip_kernel_times",
+    "mi_rank_filtered_workspace_bytes", "mi_rank_topk_filtered",
 )
 
 
@@ -118,6 +119,9 @@ def _bind(path):
         "mi_rank_topk": (ctypes.c_int, [P, I64, I64, ctypes.c_int, P, I64, I32, I64, ctypes.c_int, ctypes.c_int,
                                         P, P, P, SZ, P]),
         "mi_rank_merge": (ctypes.c_int, [P, P, I64, I64, I32, ctypes.c_int, P, P, P]),
+        "mi_rank_filtered_workspace_bytes": (SZ, [I64, I64, I32]),
+        "mi_rank_topk_filtered": (ctypes.c_int, [P, I64, I64, ctypes.c_int, P, I64, I32, I64, ctypes.c_int,
+                                                 ctypes.c_int, P, P, P, P, P, SZ, P]),
         "mi_mirror_build": (ctypes.c_int, [P, I64, I64, ctypes.c_int, P, P]),
         "mi_rank_mirror_workspace_bytes": (SZ, [I64, I64]),
         "mi_normalize_rows_f16": (ctypes.c_int, [P, I64, I64, P, P]),

@@ -1,0 +1,218 @@
+"""``FrameLibrary``: a resident multi-video index over the filtered rank kernel.
+
+The reference's UI offers a video filter whose default is all videos
+(Backend/app.py:402-429, 567-588, 605) but ranks one video's ``.npy`` per call
+(embedding_service.py:284-344), and its hybrid strategies take CLIP's
+``top_k*3`` and intersect afterwards with the frames a keyword / object filter
+allows (query_strategies.py:253-361, 466-599, 601-775).  Here every video's rows
+stay in HBM once, concatenated, and one ``rank_topk_filtered`` pass answers
+"this video", "all videos", "a video per query" and "only these frames": a
+video is a row range, an allow-list is a row mask, no corpus is copied.
+
+Rows are kept by ``EmbeddingService._corpus_on_device``'s rule: f32 rows raw,
+ranked with norm "l2"; float16 rows normalised once in NumPy's float16
+arithmetic (``normalize_rows_f16``) and ranked with norm "none".  So the library
+holds at most two concatenated corpora, one per norm mode, each with a segment
+table ``(name, offset, rows)``; a search runs one filtered pass per non-empty
+corpus and merges the two candidate lists with ``merge_topk``.
+
+Global index: the f32 ("l2") corpus' rows first, in order of addition, then the
+float16 ("none") corpus' rows, in order of addition.  Exact score ties across
+videos resolve by that global index ascending: f32 videos before float16
+videos, then the order the videos were added, then the row.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _native as N
+from .retrieval import merge_topk, normalize_rows_f16, pack_row_mask, rank_topk_filtered
+
+SORT_MIN_QUERIES = 32   # above it the queries are sorted by range begin (the kernel skips per 32-query block)
+
+
+class _Group:
+    """One concatenated corpus (one norm mode) and its segment table."""
+
+    def __init__(self, norm):
+        self.norm = norm
+        self.parts = []
+        self.segments = []      # (name, offset, rows)
+        self.rows = 0
+        self._cat = None
+
+    def append(self, name, t):
+        self.segments.append((name, self.rows, int(t.shape[0])))
+        self.parts.append(t)
+        self.rows += int(t.shape[0])
+        self._cat = None
+
+    def corpus(self):
+        import torch
+        if self._cat is None:
+            self._cat = self.parts[0] if len(self.parts) == 1 else torch.cat(self.parts, dim=0)
+            self.parts = [self._cat]
+        return self._cat
+
+    def segment(self, name):
+        for s in self.segments:
+            if s[0] == name:
+                return s
+        return None
+
+
+class FrameLibrary:
+    def __init__(self, device="cuda"):
+        self.device = device
+        self.names = []                                   # video_index -> name, order of addition
+        self._groups = [_Group("l2"), _Group("none")]     # global index order
+        self.dim = None
+
+    # ------------------------------------------------------------------ build
+    def add(self, name, rows):
+        """Append a video's embedding rows [n, D] (NumPy or torch; f32 or float16,
+        anything else is ranked as f32)."""
+        import torch
+        if name in self.names:
+            raise N.MiClipError(f"FrameLibrary: video {name!r} was already added")
+        t = torch.as_tensor(np.ascontiguousarray(rows) if isinstance(rows, np.ndarray) else rows)
+        if t.dim() != 2:
+            raise N.MiClipError("FrameLibrary.add: rows must be [n, D]")
+        if self.dim is not None and t.shape[1] != self.dim:
+            raise N.MiClipError(f"FrameLibrary.add: D = {t.shape[1]}, the library holds D = {self.dim}")
+        if t.dtype not in (torch.float32, torch.float16):
+            t = t.to(torch.float32)
+        t = t.to(self.device).contiguous()
+        if t.dtype == torch.float16:
+            if t.shape[0]:
+                t = normalize_rows_f16(t, out=t)
+            self._groups[1].append(name, t)
+        else:
+            self._groups[0].append(name, t)
+        self.dim = int(t.shape[1])
+        self.names.append(name)
+
+    def __len__(self):
+        return sum(g.rows for g in self._groups)
+
+    def segments(self):
+        """[(name, global offset, rows, norm)] in global index order."""
+        out, base = [], 0
+        for g in self._groups:
+            out += [(n, base + off, rows, g.norm) for n, off, rows in g.segments]
+            base += g.rows
+        return out
+
+    def locate(self, index):
+        """Global indices (any shape, tensor) -> (video_index int32, row int64), -1 for index -1."""
+        import torch
+        segs = self.segments()
+        idx = index.to(torch.int64)
+        if not segs:
+            neg = torch.full_like(idx, -1)
+            return neg.to(torch.int32), neg
+        starts = torch.tensor([s[1] for s in segs], dtype=torch.int64, device=idx.device)
+        vids = torch.tensor([self.names.index(s[0]) for s in segs], dtype=torch.int64, device=idx.device)
+        valid = idx >= 0
+        safe = torch.where(valid, idx, torch.zeros_like(idx))
+        # the last segment starting at or before the index (empty videos share a start: the last
+        # of them is the one that holds rows)
+        seg = torch.searchsorted(starts, safe.reshape(-1), right=True).reshape(idx.shape) - 1
+        row = torch.where(valid, safe - starts[seg], torch.full_like(idx, -1))
+        vid = torch.where(valid, vids[seg], torch.full_like(idx, -1)).to(torch.int32)
+        return vid, row
+
+    # ----------------------------------------------------------------- search
+    def _ranges(self, g, video, Q):
+        """int64 [Q, 2] host ranges of each query in group ``g``'s rows."""
+        if video is None or isinstance(video, str):
+            video = [video] * Q
+        if len(video) != Q:
+            raise N.MiClipError(f"FrameLibrary.search: {len(video)} videos for {Q} queries")
+        out = np.zeros((Q, 2), np.int64)
+        for i, v in enumerate(video):
+            if v is None:
+                out[i] = (0, g.rows)
+                continue
+            if v not in self.names:
+                raise N.MiClipError(f"FrameLibrary.search: unknown video {v!r}")
+            s = g.segment(v)
+            if s is not None:
+                out[i] = (s[1], s[1] + s[2])
+        return out
+
+    def _mask(self, g, allow):
+        """Packed mask words of group ``g`` for ``allow`` (None: no mask)."""
+        import torch
+        if allow is None:
+            return None
+        flags = np.zeros(g.rows, np.bool_)
+        for name, off, rows in g.segments:
+            a = allow.get(name)
+            if a is None or a is False:
+                continue
+            if a is True:
+                flags[off:off + rows] = True
+                continue
+            a = np.asarray(a)
+            if a.dtype == np.bool_:
+                if a.shape != (rows,):
+                    raise N.MiClipError(f"FrameLibrary.search: allow[{name!r}] has {a.shape} flags for {rows} rows")
+                flags[off:off + rows] = a
+            elif a.size:
+                a = a.astype(np.int64).reshape(-1)
+                if a.min() < 0 or a.max() >= rows:
+                    raise N.MiClipError(f"FrameLibrary.search: allow[{name!r}] holds a row outside [0, {rows})")
+                flags[off + a] = True
+        return pack_row_mask(torch.from_numpy(flags).to(self.device))
+
+    def search(self, queries, k, video=None, allow=None, nan_policy="first"):
+        """Top-k frames per query over the library.
+
+        ``video``: None (all videos), one name, or a length-Q list of names / None (each
+        query's video is its row range).  ``allow``: None or a dict name -> True | bool
+        array | index array of frame rows (the row mask); a video absent from the dict
+        is excluded.  Returns (scores f32 [Q, k], video_index int32 [Q, k], row int64
+        [Q, k]); video_index (into ``names``) and row (inside its video) are -1 and the
+        score -inf in slots beyond a query's visible frames.  1 <= k <= 64."""
+        import torch
+        q = torch.as_tensor(queries)
+        q = (q if q.dim() == 2 else q.reshape(1, -1)).to(device=self.device, dtype=torch.float32)
+        Q = q.shape[0]
+        if allow is not None:
+            unknown = [n for n in allow if n not in self.names]
+            if unknown:
+                raise N.MiClipError(f"FrameLibrary.search: unknown video {unknown[0]!r} in allow")
+        cand_s, cand_i, base = [], [], 0
+        for g in self._groups:
+            if g.rows == 0:
+                continue
+            rng = self._ranges(g, video, Q)
+            mask = self._mask(g, allow)
+            perm = None
+            qg = q
+            if Q > SORT_MIN_QUERIES:
+                # a 32-query block then shares a narrow hull of ranges, which the kernel skips around
+                perm = torch.from_numpy(np.argsort(rng[:, 0], kind="stable")).to(self.device)
+                qg = q.index_select(0, perm)
+                rng = rng[perm.cpu().numpy()]
+            s, i = rank_topk_filtered(g.corpus(), qg, k, row_mask=mask,
+                                      query_range=torch.from_numpy(rng).to(self.device), index_base=base,
+                                      norm=g.norm, nan_policy=nan_policy)
+            if perm is not None:
+                su, iu = torch.empty_like(s), torch.empty_like(i)
+                su[perm] = s
+                iu[perm] = i
+                s, i = su, iu
+            cand_s.append(s)
+            cand_i.append(i)
+            base += g.rows
+        if not cand_s:
+            s = torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device)
+            i = torch.full((Q, k), -1, dtype=torch.int64, device=self.device)
+        elif len(cand_s) == 1:
+            s, i = cand_s[0], cand_i[0]
+        else:
+            s, i = merge_topk(torch.cat(cand_s, dim=1), torch.cat(cand_i, dim=1), k, nan_policy=nan_policy)
+        vid, row = self.locate(i)
+        return s, vid, row

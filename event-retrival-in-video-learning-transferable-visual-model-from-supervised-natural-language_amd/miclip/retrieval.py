@@ -88,6 +88,87 @@ def rank_topk(corpus, queries, k, index_base=0, norm="l2", nan_policy="first"):
     return out_s[:, :kk], out_i[:, :kk]
 
 
+def pack_row_mask(mask):
+    """A bool row mask [N] as the filtered rank kernel's words: int32 [(N+31)//32],
+    bit ``r & 31`` of word ``r >> 5`` = ``mask[r]`` (``np.packbits(..., bitorder="little")``
+    viewed as little-endian uint32).  Torch ops on the mask's device: no host round trip."""
+    import torch
+    m = mask.reshape(-1).to(torch.bool)
+    n = m.shape[0]
+    words = (n + 31) // 32
+    bits = torch.zeros(words * 32, dtype=torch.int64, device=m.device)
+    bits[:n] = m
+    v = (bits.view(words, 32) << torch.arange(32, dtype=torch.int64, device=m.device)).sum(dim=1)
+    return torch.where(v >= (1 << 31), v - (1 << 32), v).to(torch.int32)
+
+
+def _row_mask(row_mask, nrows, device):
+    import torch
+    words = (nrows + 31) // 32
+    if row_mask.dtype == torch.bool:
+        if row_mask.numel() != nrows:
+            raise N.MiClipError(f"row_mask: {row_mask.numel()} flags for {nrows} rows")
+        return pack_row_mask(row_mask.to(device))
+    if row_mask.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+        raise N.MiClipError("row_mask must be a bool tensor [N] or packed int32 / uint32 words")
+    if row_mask.numel() < words:
+        raise N.MiClipError(f"row_mask: {row_mask.numel()} words for {nrows} rows ({words} needed)")
+    return row_mask.to(device).contiguous()
+
+
+def _query_range(query_range, Q, device):
+    import torch
+    if isinstance(query_range, (tuple, list)) and len(query_range) == 2 and not torch.is_tensor(query_range[0]) \
+            and not isinstance(query_range[0], (tuple, list)):
+        query_range = torch.tensor([[int(query_range[0]), int(query_range[1])]], dtype=torch.int64).expand(Q, 2)
+    r = torch.as_tensor(query_range).to(device=device, dtype=torch.int64).contiguous()
+    if r.shape != (Q, 2):
+        raise N.MiClipError(f"query_range must be [Q, 2] = {(Q, 2)} or a (begin, end) pair, got {tuple(r.shape)}")
+    return r
+
+
+def rank_topk_filtered(corpus, queries, k, row_mask=None, query_range=None, index_base=0, norm="l2",
+                       nan_policy="first"):
+    """``rank_topk`` over the rows each query may see (``mi_rank_topk_filtered``,
+    csrc/rank_filter.hip): row ``r`` is visible to query ``q`` iff ``row_mask`` is None or has
+    ``r`` set, and ``begin_q <= r < end_q``.  ``row_mask``: a device bool tensor [N] (packed on
+    the device, ``pack_row_mask``) or packed int32 / uint32 words; ``query_range``: int64 [Q, 2]
+    or one ``(begin, end)`` pair for all queries.  Indices stay global (``index_base + r``).
+
+    Returns (scores f32 [Q, k], index int64 [Q, k]) on the device; slots beyond a query's
+    visible rows are (-inf, -1).  1 <= k <= 64.  A visible row's score is bit-identical to
+    ``rank_topk``'s, so this equals ``rank_topk`` over the gathered visible rows.
+    """
+    import torch
+    if not corpus.is_cuda:
+        raise N.MiClipError("rank_topk_filtered runs on the GPU: move the corpus to the device first")
+    c = _corpus(corpus)
+    q = _queries(queries, c.device)
+    if q.shape[1] != c.shape[1]:
+        raise N.MiClipError(f"dimension mismatch: corpus D={c.shape[1]}, queries D={q.shape[1]}")
+    Nrows, D = c.shape
+    Q = q.shape[0]
+    if not 1 <= k <= REG_K:
+        raise N.MiClipError(f"rank_topk_filtered: k must be in [1, {REG_K}]")
+    if not (32 <= D <= MAX_D and D % 32 == 0):
+        raise N.MiClipError(f"D must be a multiple of 32 in [32, {MAX_D}], got {D}")
+    mask = None if row_mask is None else _row_mask(row_mask, Nrows, c.device)
+    rng = None if query_range is None else _query_range(query_range, Q, c.device)
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=c.device)
+    out_i = torch.empty((Q, k), dtype=torch.int64, device=c.device)
+    L = N.lib()
+    nbytes = L.mi_rank_filtered_workspace_bytes(Nrows, Q, k)
+    with torch.cuda.device(c.device):
+        ws = _workspace(c.device, nbytes)
+        N.check(L.mi_rank_topk_filtered(c.data_ptr(), Nrows, D, N.dtype_code(c.dtype), q.data_ptr(), Q, k,
+                                        int(index_base), _NORMS[norm], _NANS[nan_policy],
+                                        mask.data_ptr() if mask is not None else None,
+                                        rng.data_ptr() if rng is not None else None,
+                                        out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        N.stream_ptr(c.device)), "mi_rank_topk_filtered")
+    return out_s, out_i
+
+
 def normalize_rows_f16(rows, out=None):
     """``embeddings / np.linalg.norm(embeddings, axis=-1, keepdims=True)`` for a
     float16 corpus, bit for bit as NumPy evaluates it in float16

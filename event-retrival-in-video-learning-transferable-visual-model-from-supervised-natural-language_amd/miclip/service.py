@@ -31,6 +31,7 @@ import numpy as np
 
 from . import api
 from .preprocess import decode_chunk, load_frames
+from .library import FrameLibrary
 from .retrieval import MirroredCorpus, normalize_rows_f16, rank_topk
 
 # corpora from this many rows on also get an fp16 ranking mirror (scripts/mirror_micro.py:
@@ -124,6 +125,7 @@ class EmbeddingService:
         self.checkpoint_path = checkpoint_path or os.environ.get("CLIP_FINETUNED_CHECKPOINT", "")
         self._device_corpus = {}
         self._mirrors = {}          # id(device corpus) -> MirroredCorpus (large corpora)
+        self._library = None        # (video names, embedding paths, mtimes, FrameLibrary)
         self._lookup = {}
         if self.checkpoint_path and os.path.exists(self.checkpoint_path):
             try:
@@ -286,6 +288,58 @@ class EmbeddingService:
             return top_frames
         except Exception as e:
             print(f"Error in search_top_frames: {e}")
+            return []
+
+    def _frame_library(self, video_names):
+        """One resident ``FrameLibrary`` over the videos' embedding files, rebuilt when the
+        list of videos or a file's mtime changes (``_corpus_on_device``'s invalidation);
+        None when a file is missing."""
+        names = tuple(video_names)
+        paths = tuple(self.path_service.get_embeddings_path(v) for v in names)
+        if not all(os.path.exists(p) for p in paths):
+            return None
+        mtimes = tuple(os.path.getmtime(p) for p in paths)
+        hit = self._library
+        if hit is not None and hit[:3] == (names, paths, mtimes):
+            return hit[3]
+        lib = FrameLibrary(device=self.original_model.device)
+        for v, p in zip(names, paths):
+            lib.add(v, np.load(p))
+        self._library = (names, paths, mtimes, lib)
+        return lib
+
+    def search_top_frames_all(self, query, top_k, video_names, allow_frames=None):
+        """``search_top_frames`` over several videos at once (the UI's "all videos" filter,
+        app.py:402-429, 567-588, 605): ``[(video_name, frame), ...]``, best first, from one
+        filtered pass over the resident library (at most ``top_k`` <= 64 entries).
+        ``allow_frames``: optional dict video -> iterable of frame basenames (what
+        ``search_frames_by_keyword`` returns); then only those frames are ranked -- the exact
+        form of the hybrid strategies' "CLIP top_k*3, then intersect" -- and a video absent
+        from the dict is excluded.  Errors are swallowed to ``[]`` as in ``search_top_frames``."""
+        try:
+            video_names = list(video_names)
+            if not video_names or int(top_k) <= 0:
+                return []
+            lib = self._frame_library(video_names)
+            if lib is None:
+                return []
+            frames = {v: self._frames(v) for v in video_names}
+            allow = None
+            if allow_frames is not None:
+                allow = {}
+                for v, wanted in allow_frames.items():
+                    if v not in frames:
+                        continue
+                    wanted = {os.path.basename(f) for f in wanted}
+                    allow[v] = np.array([i for i, f in enumerate(frames[v]) if os.path.basename(f) in wanted],
+                                        dtype=np.int64)
+            text_features = self.get_text_features(query, None)
+            k = min(int(top_k), max(len(lib), 1))
+            _, vid, row = lib.search(np.asarray(text_features, dtype=np.float32).reshape(1, -1), k, allow=allow)
+            vid, row = vid[0].cpu().numpy(), row[0].cpu().numpy()
+            return [(lib.names[v], frames[lib.names[v]][r]) for v, r in zip(vid, row) if v >= 0]
+        except Exception as e:
+            print(f"Error in search_top_frames_all: {e}")
             return []
 
     def search_top_frames_by_image(self, image_features, top_k, video_name=None):

@@ -149,6 +149,37 @@ int mi_rank_topk(const void* corpus, int64_t N, int64_t D, int corpus_dtype,
                  int norm_mode, int nan_policy, float* out_scores, int64_t* out_index,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* Workspace bytes mi_rank_topk_filtered needs for (N, Q, k); 0 for k outside [1, 64]. */
+size_t mi_rank_filtered_workspace_bytes(int64_t N, int64_t Q, int32_t k);
+
+/* mi_rank_topk over the rows a request may see: the same fused pass (per row L2
+ * norm + fp32-exact dot + top-k, a visible row's score bit-identical to
+ * mi_rank_topk's / mi_score_matrix's), restricted by a row bitmask and / or a
+ * per-query row range.  Serves the UI's video filter, whose default is all
+ * videos (Backend/app.py:402-429, 567-588, 605): one resident library of
+ * videos, a row range per video or per query; and the hybrid strategies'
+ * candidate sets (query_strategies.py:253-361, 466-599, 601-775: CLIP top_k*3
+ * intersected with the frames a keyword / object filter allows), whose exact
+ * form is the top-k among the allowed frames.
+ * Row r is visible to query q iff (row_mask == NULL or bit r & 31 of word
+ * r >> 5 is set) and begin_q <= r < end_q.  row_mask: device, (N+31)/32 words
+ * (bits at or beyond N are ignored) or NULL = every row; query_range: device
+ * int64 [Q][2] = [begin, end), clipped to [0, N), begin >= end = nothing, or
+ * NULL = [0, N) for every query.  Only visible rows are ranked or returned
+ * (NaN rows under MI_NAN_FIRST included); 32-row tiles without a visible row
+ * for a block of 32 queries are neither loaded nor scored.  Both arrays are
+ * read by the kernel: no synchronisation, capturable.
+ * out_scores f32 [Q,k], out_index int64 [Q,k]: global index = index_base + r,
+ * score descending then index ascending, NaN by nan_policy; slots beyond a
+ * query's visible rows are index -1, score -inf.  1 <= k <= 64
+ * (MI_ERR_UNSUPPORTED above), D as mi_rank_topk. */
+int mi_rank_topk_filtered(const void* corpus, int64_t N, int64_t D, int corpus_dtype,
+                          const float* queries, int64_t Q, int32_t k, int64_t index_base,
+                          int norm_mode, int nan_policy,
+                          const uint32_t* row_mask, const int64_t* query_range,
+                          float* out_scores, int64_t* out_index,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Ranking mirror of a corpus for mi_rank_mirror (an
  * HBM-resident half-width mirror beside the f32 master of
  * EmbeddingService.get_embeddings, embedding_service.py:186-217).
