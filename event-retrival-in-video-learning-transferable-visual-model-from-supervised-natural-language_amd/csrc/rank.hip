@@ -25,54 +25,13 @@
 
 #include "common.hpp"
 #include "internal.hpp"
-#include "rank_keys.hpp"
+#include "rank_pass.hpp"
 
 namespace miclip {
 namespace {
 using namespace rankk;
 
-constexpr int RQ = 32;          // queries per workgroup (MFMA N)
-constexpr int ROWS_WAVE = 32;   // corpus rows per wave tile (MFMA M)
-
-
-
-
-// Computes the 32x32 f32 score tile of (rows row0.., queries of this block)
-// for one wave.  Returns acc (C layout: col = query = lane&31,
-// row = (r&3) + 8*(r>>2) + 4*(lane>>5)) and the per-row sum of squares in
-// nrm (LDS, 32 floats for this wave).
-template <int DT>
-__device__ __forceinline__ void score_tile(const void* corpus, int64_t N, int64_t D, int64_t row0,
-                                           const float* Ts, int ts_stride, float* nrm, f32x16& acc) {
-  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-  const int64_t row = min(row0 + r, N - 1);
-  acc = f32x16{};
-  float ss = 0.f;
-  float cur[16], nxt[16];
-  load_chunk<DT>(corpus, row, D, 16 * h, cur);
-  const int nch = (int)(D / 32);
-  const float* tq = Ts + r * ts_stride + 16 * h;
-  for (int j = 0; j < nch; ++j) {
-    if (j + 1 < nch) load_chunk<DT>(corpus, row, D, 32 * (j + 1) + 16 * h, nxt);
-    float tb[16];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 t = *(const float4*)(tq + 32 * j + 4 * i);
-      tb[4 * i] = t.x; tb[4 * i + 1] = t.y; tb[4 * i + 2] = t.z; tb[4 * i + 3] = t.w;
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(cur[i], tb[i], acc, 0, 0, 0);
-      ss = fmaf(cur[i], cur[i], ss);
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) cur[i] = nxt[i];
-  }
-  ss += __shfl_xor(ss, 32, 64);
-  if (h == 0) nrm[r] = ss;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
+constexpr int RQ = FQ;          // queries per workgroup (MFMA N)
 
 // Streaming stage 1 (the default for k <= 16, rank_stream): the same
 // 32-row x 32-query wave tiles and exact-f32 MFMA arithmetic as rank_stage1,
@@ -98,145 +57,38 @@ __device__ __forceinline__ void score_tile(const void* corpus, int64_t N, int64_
 //    top-k (that list already holds k better rows).
 // LDS: queries [32][D+4] f32, row norms [NW][32], tau [32]; the lists
 // [64*NW lanes][16] (key u32, idx i32) reuse the query area after a barrier.
-
+// The pass itself is rank_pass.hpp's stream_pass over AllRows (rank_filter_stream
+// runs the same body over FilteredRows).
 template <int DT, int NW, bool SPLITM = true>
 __global__ __launch_bounds__(64 * NW) void rank_stream(const void* __restrict__ corpus, int64_t N, int64_t D,
                                                        const float* __restrict__ queries, int64_t Q, int k,
                                                        int64_t rows_per_wg, int norm_mode, int nan_first,
                                                        int64_t index_base, FoldWs f, float* __restrict__ out_s,
                                                        int64_t* __restrict__ out_i) {
-  constexpr int NT = 64 * NW, KC = 16;
+  constexpr int KC = 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int ts_stride = (int)D + 4;
   float* Ts = (float*)smem;
   float* nrm_all = Ts + RQ * ts_stride;
   uint32_t* tau = (uint32_t*)(nrm_all + NW * 32);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
   const int64_t q0 = (int64_t)QB * RQ;
 
-  for (int64_t e = tid; e < RQ * D; e += NT) {
-    const int qq = (int)(e / D);
-    const int64_t d = e % D;
-    Ts[qq * ts_stride + d] = (q0 + qq < Q) ? queries[(q0 + qq) * D + d] : 0.f;
-  }
+  stage_queries(Ts, ts_stride, queries, D, q0, Q, 64 * NW);
   if (tid < RQ) tau[tid] = 0u;
   __syncthreads();
 
   const int64_t r_begin = (int64_t)RB * rows_per_wg;
   const int64_t r_end = min(N, r_begin + rows_per_wg);
-  float* nrm = nrm_all + wave * 32;
-  const int64_t ntw = (r_end - r_begin + 31) / 32;
-  const int my_tiles = ntw > wave ? (int)((ntw - 1 - wave) / NW + 1) : 0;
-  const int nch = (int)(D / 32);
-  const int64_t total = (int64_t)my_tiles * nch;
-  const int nrows = (int)(r_end - r_begin);
-
-  uint64_t L[KC];
-#pragma unroll
-  for (int p = 0; p < KC; ++p) L[p] = 0ull;      // (key 0, row ~0): below every real candidate
-  const bool qvalid = q0 + r < Q;
-  const float* tq = Ts + r * ts_stride + 16 * h;
-
-  int lt = 0, lj = 0;  // load cursor (tile ordinal, chunk); loads past the end re-read a valid row
-  auto next_load = [&](float (&buf)[16]) {
-    const int64_t row = min(r_begin + (int64_t)(wave + NW * lt) * 32 + r, N - 1);
-    load_chunk<DT>(corpus, row, D, 32 * lj + 16 * h, buf);
-    if (++lj == nch) { lj = 0; ++lt; }
-  };
-  int ct = 0, cj = 0;  // compute cursor
-  f32x16 acc = f32x16{};
-  float ss = 0.f;
-  auto finalize = [&]() {
-    ss += __shfl_xor(ss, 32, 64);
-    if (h == 0) nrm[r] = inv_norm(ss, norm_mode);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    const int tr0 = (wave + NW * ct) * 32;           // tile's first row, relative to r_begin
-    const uint32_t tq_thr = tau[r];
-    const uint32_t own = (uint32_t)(L[KC - 1] >> 32);
-    const uint32_t thr = own > tq_thr ? own : tq_thr;
-    uint64_t c[16];
-    bool any = false;
-    uint32_t okm = 0u;
-#pragma unroll
-    for (int rg = 0; rg < 16; ++rg) {
-      const int rr = (rg & 3) + 8 * (rg >> 2) + 4 * h;
-      const int lr = tr0 + rr;
-      const float sc = norm_mode == 2 ? acc[rg] : acc[rg] * nrm[rr];
-      const uint32_t key = score_key(sc, nan_first);
-      const bool ok = qvalid && lr < nrows && key >= thr;
-      c[rg] = ok ? (((uint64_t)key << 32) | (uint32_t)~(uint32_t)lr) : 0ull;
-      any |= ok;
-      okm |= ok ? 1u << rg : 0u;
+  const bool qvalid = q0 + (lane & 31) < Q;
+  stream_pass<DT, NW>(corpus, N, D, Ts, ts_stride, nrm_all + wave * 32, tau, wave, lane, r_begin, qvalid, k, norm_mode,
+                      nan_first, AllRows(r_begin, r_end, wave, NW, qvalid), [&](uint64_t (&L)[KC]) {
+    if (SPLITM) {   // split merge: the workgroup's top-k published, then fold_merge_kernel
+      lines_publish<NW>(L, smem, wave, lane, q0, Q, k, r_begin, f);   // (its first barrier: the query area is free)
+      return;
     }
-    if (__any(any)) {
-      list_update16(L, c, okm);
-      // publish this list's k-th key (a lower bound of the query's k-th best)
-      uint32_t kth = (uint32_t)(L[0] >> 32);
-#pragma unroll
-      for (int p = 1; p < KC; ++p) kth = (p == k - 1) ? (uint32_t)(L[p] >> 32) : kth;
-      const uint32_t other = (uint32_t)__shfl_xor((int)kth, 32, 64);
-      kth = kth > other ? kth : other;
-      if (h == 0 && qvalid && kth > tq_thr) tau_max(&tau[r], kth);
-    }
-    __builtin_amdgcn_wave_barrier();
-    acc = f32x16{};
-    ss = 0.f;
-    ++ct;
-    cj = 0;
-  };
-  auto consume = [&](const float (&buf)[16]) {
-    float tb[16];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 t = *(const float4*)(tq + 32 * cj + 4 * i);
-      tb[4 * i] = t.x; tb[4 * i + 1] = t.y; tb[4 * i + 2] = t.z; tb[4 * i + 3] = t.w;
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(buf[i], tb[i], acc, 0, 0, 0);
-      ss = fmaf(buf[i], buf[i], ss);
-    }
-    if (++cj == nch) finalize();
-  };
-
-  // Three register buffers used in place, loaded two chunks ahead (hipcc's
-  // own counted waits; measured 3.8-4.0 TB/s at 1M rows).  Tried and
-  // rejected: a padded exit-free body with sched_barriers (hipcc then drained
-  // the ring at the back-edge) and inline-asm loads with hand-counted waits
-  // (hipcc copies the in-flight registers).
-  if (total > 0) {
-    float b0[16], b1[16], b2[16];
-    next_load(b0);
-    next_load(b1);
-    for (int64_t c = 0; c < total; c += 3) {
-      next_load(b2);
-      consume(b0);
-      if (c + 1 >= total) break;
-      next_load(b0);
-      consume(b1);
-      if (c + 2 >= total) break;
-      next_load(b1);
-      consume(b2);
-    }
-  }
-  if (SPLITM) {   // split merge: the workgroup's top-k published, then fold_merge_kernel
-    lines_publish<NW>(L, smem, wave, lane, q0, Q, k, r_begin, f);   // (its first barrier: the query area is free)
-    return;
-  }
-  __syncthreads();  // query area free -> lists
-  uint32_t* Lk = (uint32_t*)smem;
-  int32_t* Li = (int32_t*)(smem + NT * KC * 4);
-#pragma unroll
-  for (int p = 0; p < KC; ++p) {
-    const bool real = L[p] != 0ull;
-    Lk[tid * KC + p] = real ? (uint32_t)(L[p] >> 32) : 0u;
-    Li[tid * KC + p] = real ? (int32_t)~(uint32_t)L[p] : INT_MAX;
-  }
-  __syncthreads();
-  fold_publish<2 * NW>(Lk, Li, KC, q0, Q, k, r_begin, f);
-  fold_reduce<NT>(smem, f, q0, Q, k, nan_first, index_base, out_s, out_i);
+    fold_tail<NW>(L, smem, q0, Q, k, nan_first, r_begin, index_base, f, out_s, out_i);
+  });
 }
 
 // Register-query streaming stage 1 (f32 corpus, D = 512, k <= 16:
@@ -485,13 +337,13 @@ __global__ __launch_bounds__(256) void rank_reg(const void* __restrict__ corpus,
       uint64_t c[16];
       bool any = false;
       uint32_t okm = 0u;
-      // the 16 rows' reciprocals: rows (rg & 3) + 8 (rg >> 2) + 4 h are four 16-byte runs
+      // the 16 rows' reciprocals: rows c_row(rg, h) are four 16-byte runs
       f32x4 nv[4];
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4) nv[q4] = *(const f32x4*)(nrm + 8 * q4 + 4 * h);
 #pragma unroll
       for (int rg = 0; rg < 16; ++rg) {
-        const int rr = (rg & 3) + 8 * (rg >> 2) + 4 * h;
+        const int rr = c_row(rg, h);
         const int lr = tr0 + rr;
         const float sc = norm_mode == 2 ? acc[rg] : acc[rg] * nv[rg >> 2][rg & 3];
         const uint32_t key = score_key(sc, nan_first);
@@ -520,20 +372,7 @@ __global__ __launch_bounds__(256) void rank_reg(const void* __restrict__ corpus,
     lines_publish<NW>(L, smem, wave, lane, q0, Q, k, r_begin, f);
     return;
   }
-  __syncthreads();   // ring free -> lists
-  if (STAMP && tid == 0) stamp[2] = __builtin_amdgcn_s_memrealtime();
-  uint32_t* Lk = (uint32_t*)smem;
-  int32_t* Li = (int32_t*)(smem + NT * KC * 4);
-#pragma unroll
-  for (int p = 0; p < KC; ++p) {
-    const bool real = L[p] != 0ull;
-    Lk[tid * KC + p] = real ? (uint32_t)(L[p] >> 32) : 0u;
-    Li[tid * KC + p] = real ? (int32_t)~(uint32_t)L[p] : INT_MAX;
-  }
-  __syncthreads();
-  fold_publish<2 * NW>(Lk, Li, KC, q0, Q, k, r_begin, f);
-  if (STAMP && tid == 0) stamp[3] = __builtin_amdgcn_s_memrealtime();
-  fold_reduce<NT>(smem, f, q0, Q, k, nan_first, index_base, out_s, out_i, STAMP ? stamp : nullptr);
+  fold_tail<NW>(L, smem, q0, Q, k, nan_first, r_begin, index_base, f, out_s, out_i, STAMP ? stamp : nullptr);
   if (STAMP && tid == 0) stamp[4] = __builtin_amdgcn_s_memrealtime();
 }
 
@@ -552,84 +391,13 @@ __global__ __launch_bounds__(256) void rank_stage1(const void* __restrict__ corp
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t q0 = (int64_t)QB * RQ;
 
-  for (int64_t e = tid; e < RQ * D; e += 256) {
-    const int qq = (int)(e / D);
-    const int64_t d = e % D;
-    Ts[qq * ts_stride + d] = (q0 + qq < Q) ? queries[(q0 + qq) * D + d] : 0.f;
-  }
+  stage_queries(Ts, ts_stride, queries, D, q0, Q, 256);
   __syncthreads();
 
   const int64_t r_begin = (int64_t)RB * rows_per_wg;
   const int64_t r_end = min(N, r_begin + rows_per_wg);
-  float* nrm = nrm_all + wave * 32;
-
-  uint32_t lk[KC];
-  int32_t li[KC];
-#pragma unroll
-  for (int p = 0; p < KC; ++p) { lk[p] = 0u; li[p] = INT_MAX; }
-
-  const int qcol = lane & 31, h = lane >> 5;
-  const bool qvalid = q0 + qcol < Q;
-  for (int64_t t0 = r_begin + wave * ROWS_WAVE; t0 < r_end; t0 += 4 * ROWS_WAVE) {
-    f32x16 acc;
-    score_tile<DT>(corpus, N, D, t0, Ts, ts_stride, nrm, acc);
-#pragma unroll
-    for (int rg = 0; rg < 16; ++rg) {
-      const int rr = (rg & 3) + 8 * (rg >> 2) + 4 * h;
-      const int64_t row = t0 + rr;
-      const float sc = apply_norm(acc[rg], nrm[rr], norm_mode);
-      const uint32_t key = score_key(sc, nan_first);
-      const int32_t li_row = (int32_t)(row - r_begin);
-      const bool ok = qvalid && row < r_end && better(key, li_row, lk[KC - 1], li[KC - 1]);
-      if (__builtin_expect(__any(ok), 0)) {
-        if (ok) list_insert<KC, int32_t>(lk, li, key, li_row);
-      }
-    }
-  }
-  __syncthreads();  // query area free -> lists
-  uint32_t* Lk = (uint32_t*)smem;
-  int32_t* Li = (int32_t*)(smem + 256 * KC * 4);
-#pragma unroll
-  for (int p = 0; p < KC; ++p) {
-    Lk[tid * KC + p] = lk[p];
-    Li[tid * KC + p] = li[p];
-  }
-  __syncthreads();
-  if (tid < RQ && q0 + tid < Q) {
-    // 8 sorted lists: lanes {w*64 + tid, w*64 + 32 + tid}
-    int pos[8];
-#pragma unroll
-    for (int l = 0; l < 8; ++l) pos[l] = 0;
-    float* os = ws_s + (q0 + tid) * C + (int64_t)RB * k;
-    int64_t* oi = ws_i + (q0 + tid) * C + (int64_t)RB * k;
-    for (int o = 0; o < k; ++o) {
-      uint32_t bk = 0u;
-      int32_t bi = INT_MAX;
-      int bl = 0;
-#pragma unroll
-      for (int l = 0; l < 8; ++l) {
-        const int src = (l >> 1) * 64 + (l & 1) * 32 + tid;
-        if (pos[l] < KC) {
-          const uint32_t kk = Lk[src * KC + pos[l]];
-          const int32_t ii = Li[src * KC + pos[l]];
-          if (better(kk, ii, bk, bi)) { bk = kk; bi = ii; bl = l; }
-        }
-      }
-#pragma unroll
-      for (int l = 0; l < 8; ++l) pos[l] += (l == bl) ? 1 : 0;
-      if (bi == INT_MAX) {
-        os[o] = -INFINITY;
-        oi[o] = -1;
-      } else {
-        // decode: exact inverse of score_key for non-NaN keys
-        float s;
-        if ((bk == 0xFFFFFFFFu && nan_first) || (bk == 0u && !nan_first)) s = __uint_as_float(0x7fc00000u);
-        else s = __uint_as_float((bk & 0x80000000u) ? (bk & 0x7fffffffu) : ~bk);
-        os[o] = s;
-        oi[o] = index_base + r_begin + bi;
-      }
-    }
-  }
+  tiles_pass<KC, DT>(corpus, N, D, smem, Ts, ts_stride, nrm_all + wave * 32, wave, r_begin, q0, Q, k, norm_mode,
+                     nan_first, index_base, AllRows(r_begin, r_end, wave, 4, q0 + (lane & 31) < Q), ws_s, ws_i, C);
 }
 
 // One workgroup per query: threads keep strided top-KC lists, then a tree
@@ -684,10 +452,7 @@ __global__ __launch_bounds__(NT) void rank_merge_kernel(const float* __restrict_
         out_s[q * k + o] = -INFINITY;
         out_i[q * k + o] = -1;
       } else {
-        float s;
-        if ((bk == 0xFFFFFFFFu && nan_first) || (bk == 0u && !nan_first)) s = __uint_as_float(0x7fc00000u);
-        else s = __uint_as_float((bk & 0x80000000u) ? (bk & 0x7fffffffu) : ~bk);
-        out_s[q * k + o] = s;
+        out_s[q * k + o] = decode_key(bk, nan_first);
         out_i[q * k + o] = bi;
       }
     }
@@ -801,11 +566,7 @@ __global__ __launch_bounds__(256) void score_matrix_kernel(const void* __restric
   float* nrm_all = Ts + RQ * ts_stride;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t q0 = (int64_t)blockIdx.y * RQ;
-  for (int64_t e = tid; e < RQ * D; e += 256) {
-    const int qq = (int)(e / D);
-    const int64_t d = e % D;
-    Ts[qq * ts_stride + d] = (q0 + qq < Q) ? queries[(q0 + qq) * D + d] : 0.f;
-  }
+  stage_queries(Ts, ts_stride, queries, D, q0, Q, 256);
   __syncthreads();
   const int64_t t0 = ((int64_t)blockIdx.x * 4 + wave) * ROWS_WAVE;
   if (t0 >= N) return;
@@ -815,7 +576,7 @@ __global__ __launch_bounds__(256) void score_matrix_kernel(const void* __restric
   if (q0 + qcol >= Q) return;
 #pragma unroll
   for (int rg = 0; rg < 16; ++rg) {
-    const int rr = (rg & 3) + 8 * (rg >> 2) + 4 * h;
+    const int rr = c_row(rg, h);
     if (t0 + rr < N) out[(q0 + qcol) * N + t0 + rr] = apply_norm(acc[rg], nrm_all[wave * 32 + rr], norm_mode);
   }
 }
@@ -1105,23 +866,6 @@ size_t rank_workspace_bytes(int64_t N, int64_t Q, int k) {
   return cert ? al128(rank_cert_ws_bytes(N, Q)) + exact : exact;
 }
 
-static size_t stage1_lds(int64_t D, int KC) {
-  const size_t qa = (size_t)RQ * (D + 4) * 4 + 4 * 32 * 4;
-  const size_t la = (size_t)256 * KC * 8;
-  return qa > la ? qa : la;
-}
-
-template <int KC, int DT>
-static hipError_t launch_stage1(dim3 grid, size_t lds, hipStream_t s, const void* corpus, int64_t N, int64_t D,
-                                const float* q, int64_t Q, int k, int64_t rpw, int nm, int nf, int64_t base,
-                                float* ws_s, int64_t* ws_i, int64_t C) {
-  auto fn = rank_stage1<KC, DT>;
-  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, corpus, N, D, q, Q, k, rpw, nm, nf, base, ws_s, ws_i, C);
-  return hipGetLastError();
-}
-
 hipError_t rank_merge(const float* cs, const int64_t* ci, int64_t Q, int64_t C, int k, int nan_first, float* out_s,
                       int64_t* out_i, hipStream_t s) {
   if (Q <= 0) return hipSuccess;
@@ -1215,12 +959,11 @@ static hipError_t launch_reg(int64_t N, const void* corpus, const float* q, int6
   auto fn = rank_reg<D, 8, 6, false, false, false, DT>;
   constexpr bool inl = false;
 #endif
-  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
+  hipError_t e = hipSuccess;
   if (!prezeroed && (e = fold_zero(f, s)) != hipSuccess) return e;
   const dim3 grid((unsigned)((Q + RQ - 1) / RQ), (unsigned)nwg);   // (query blocks, row blocks): RB / QB
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, corpus, N, q, Q, k, rpw, nm, nf, base, f, out_s, out_i, gate);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = launch_lds(fn, grid, 256, lds, s, corpus, N, q, Q, k, rpw, nm, nf, base, f, out_s, out_i, gate)) != hipSuccess)
+    return e;
 #if MICLIP_AB
   if (inl || (stp && stp[0] == '1')) return hipSuccess;
 #endif
@@ -1228,22 +971,23 @@ static hipError_t launch_reg(int64_t N, const void* corpus, const float* q, int6
 }
 
 template <int DT, int NW>
-static hipError_t launch_stream(dim3 grid, size_t lds, hipStream_t s, const void* corpus, int64_t N, int64_t D,
-                                const float* q, int64_t Q, int k, int64_t rpw, int nm, int nf, int64_t base,
-                                void* ws, float* out_s, int64_t* out_i) {
+static hipError_t launch_stream(dim3 grid, hipStream_t s, const void* corpus, int64_t N, int64_t D, const float* q,
+                                int64_t Q, int k, int64_t rpw, int nm, int nf, int64_t base, void* ws, float* out_s,
+                                int64_t* out_i) {
   bool inl = false;   // the in-launch merge (A/B: MICLIP_RANK_FOLD=1)
 #if MICLIP_AB
   const char* fold = getenv("MICLIP_RANK_FOLD");
   inl = fold && fold[0] == '1';
 #endif
   auto fn = inl ? rank_stream<DT, NW, false> : rank_stream<DT, NW, true>;
-  const size_t l = lds > fold_lds(64 * NW) ? lds : fold_lds(64 * NW);
-  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l);
-  if (e != hipSuccess) return e;
+  // tail: the (key, idx) lists [64 NW lanes][16] or the in-launch reducer's area
+  const size_t lists = (size_t)64 * NW * 16 * 8;
+  const size_t l = stream_lds(D, NW, lists > fold_lds(64 * NW) ? lists : fold_lds(64 * NW));
   const FoldWs f = fold_ws(ws, grid.y, Q);
-  if ((e = fold_zero(f, s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(fn, grid, dim3(64 * NW), l, s, corpus, N, D, q, Q, k, rpw, nm, nf, base, f, out_s, out_i);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipError_t e = fold_zero(f, s);
+  if (e != hipSuccess) return e;
+  if ((e = launch_lds(fn, grid, 64 * NW, l, s, corpus, N, D, q, Q, k, rpw, nm, nf, base, f, out_s, out_i)) != hipSuccess)
+    return e;
   return inl ? hipSuccess : fold_merge(f, grid.y, Q, k, nf, base, out_s, out_i, nullptr, s);
 }
 
@@ -1252,8 +996,8 @@ hipError_t rank_topk(const void* corpus, int64_t N, int64_t D, int dt, const flo
                      hipStream_t s) {
   if (k > RANK_REG_K) return rank_topk_large(corpus, N, D, dt, q, Q, k, base, norm_mode, nan_first, out_s, out_i, ws, s);
   const int64_t nch = rank_chunks(N);
-  const int64_t rpw = ((N + nch - 1) / nch + 383) / 384 * 384;
-  const int64_t nwg = (N + rpw - 1) / rpw;
+  const RowSplit split = row_split(N, nch);
+  const int64_t rpw = split.rpw, nwg = split.nwg;
   const int64_t C = nwg * k;
   float* ws_s = (float*)ws;
   int64_t* ws_i = (int64_t*)((char*)ws + (size_t)(Q * nch * k) * sizeof(float));
@@ -1269,14 +1013,9 @@ hipError_t rank_topk(const void* corpus, int64_t N, int64_t D, int dt, const flo
   const char* legacy = getenv("MICLIP_RANK_STAGE1");   // A/B: the previous one-tile-at-a-time kernel
   const char* noreg = getenv("MICLIP_RANK_REG");        // A/B: 0 = rank_stream for f32 D = 512 too
 #else
-  constexpr int NW = 12;
   const char* legacy = nullptr;
   const char* noreg = nullptr;
 #endif
-  const size_t qa = (size_t)RQ * (D + 4) * 4 + (size_t)NW * 32 * 4 + RQ * 4;
-  const size_t la = (size_t)64 * NW * KC * 8;
-  const size_t lds = qa > la ? qa : la;
-  hipError_t e;
   if (KC == 16 && D == 512 && !(legacy && legacy[0] == '1') && !(noreg && noreg[0] == '0')) {
     if (rank_cert_eligible(N, D, dt, k, norm_mode)) {
       // certified bf16-MFMA pass + exact re-score of its candidates, then the exact pass for
@@ -1287,46 +1026,43 @@ hipError_t rank_topk(const void* corpus, int64_t N, int64_t D, int dt, const flo
       hipError_t ec = rank_cert_topk(corpus, N, dt, q, Q, k, base, norm_mode, nan_first, out_s, out_i, ws, &cert, s,
                                      fold_zero_base(f2), fold_zero_words(f2));
       if (ec != hipSuccess) return ec;
-      return dt == 0 ? launch_reg<512, 0>(N, corpus, q, Q, k, norm_mode, nan_first, base, ws2, out_s, out_i, s, cert, true)
-                     : launch_reg<512, 1>(N, corpus, q, Q, k, norm_mode, nan_first, base, ws2, out_s, out_i, s, cert, true);
+      return dispatch_dt(dt, [&](auto DT) {   // (eligible: f32 or bf16 rows)
+        return launch_reg<512, DT()>(N, corpus, q, Q, k, norm_mode, nan_first, base, ws2, out_s, out_i, s, cert, true);
+      });
     }
     // (D = 768 would hold 384 query VGPRs: hipcc spills ~230, so it keeps rank_stream)
-    return dt == 0   ? launch_reg<512, 0>(N, corpus, q, Q, k, norm_mode, nan_first, base, ws, out_s, out_i, s)
-           : dt == 1 ? launch_reg<512, 1>(N, corpus, q, Q, k, norm_mode, nan_first, base, ws, out_s, out_i, s)
-                     : launch_reg<512, 2>(N, corpus, q, Q, k, norm_mode, nan_first, base, ws, out_s, out_i, s);
+    return dispatch_dt(dt, [&](auto DT) {
+      return launch_reg<512, DT()>(N, corpus, q, Q, k, norm_mode, nan_first, base, ws, out_s, out_i, s);
+    });
   }
   if (KC == 64 || (legacy && legacy[0] == '1')) {
-#define MI_S1(KCV, DTV) \
-  launch_stage1<KCV, DTV>(grid, stage1_lds(D, KCV), s, corpus, N, D, q, Q, k, rpw, norm_mode, nan_first, base, ws_s, \
-                          ws_i, C)
-    if (KC == 16) e = dt == 0 ? MI_S1(16, 0) : dt == 1 ? MI_S1(16, 1) : MI_S1(16, 2);
-    else e = dt == 0 ? MI_S1(64, 0) : dt == 1 ? MI_S1(64, 1) : MI_S1(64, 2);
-#undef MI_S1
+    const hipError_t e = dispatch_dt(dt, [&](auto DT) {
+      auto stage1 = [&](auto fn, int kc) {
+        return launch_lds(fn, grid, 256, stage1_lds(D, kc), s, corpus, N, D, q, Q, k, rpw, norm_mode, nan_first, base,
+                          ws_s, ws_i, C);
+      };
+      return KC == 16 ? stage1(rank_stage1<16, DT()>, 16) : stage1(rank_stage1<64, DT()>, 64);
+    });
     if (e != hipSuccess) return e;
     return rank_merge(ws_s, ws_i, Q, C, k, nan_first, out_s, out_i, s);
   }
-  // k <= 16: rank_stream with the in-launch merge
-#define MI_RS(DTV, NWV) \
-  launch_stream<DTV, NWV>(grid, lds, s, corpus, N, D, q, Q, k, rpw, norm_mode, nan_first, base, ws, out_s, out_i)
+  // k <= 16: rank_stream with the split (or, A/B, in-launch) merge
+  return dispatch_dt(dt, [&](auto DT) {
 #if MICLIP_AB
-  if (NW == 8) return dt == 0 ? MI_RS(0, 8) : dt == 1 ? MI_RS(1, 8) : MI_RS(2, 8);
+    if (NW == 8)
+      return launch_stream<DT(), 8>(grid, s, corpus, N, D, q, Q, k, rpw, norm_mode, nan_first, base, ws, out_s, out_i);
 #endif
-  return dt == 0 ? MI_RS(0, 12) : dt == 1 ? MI_RS(1, 12) : MI_RS(2, 12);
-#undef MI_RS
+    return launch_stream<DT(), 12>(grid, s, corpus, N, D, q, Q, k, rpw, norm_mode, nan_first, base, ws, out_s, out_i);
+  });
 }
 
 hipError_t score_matrix(const void* corpus, int64_t N, int64_t D, int dt, const float* q, int64_t Q, int norm_mode,
                         float* out, hipStream_t s) {
   const dim3 grid((unsigned)((N + 127) / 128), (unsigned)((Q + RQ - 1) / RQ));
-  const size_t lds = (size_t)RQ * (D + 4) * 4 + 4 * 32 * 4;
-  const void* fn = dt == 0 ? (const void*)score_matrix_kernel<0>
-                           : dt == 1 ? (const void*)score_matrix_kernel<1> : (const void*)score_matrix_kernel<2>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  if (dt == 0) hipLaunchKernelGGL(score_matrix_kernel<0>, grid, dim3(256), lds, s, corpus, N, D, q, Q, norm_mode, out);
-  else if (dt == 1) hipLaunchKernelGGL(score_matrix_kernel<1>, grid, dim3(256), lds, s, corpus, N, D, q, Q, norm_mode, out);
-  else hipLaunchKernelGGL(score_matrix_kernel<2>, grid, dim3(256), lds, s, corpus, N, D, q, Q, norm_mode, out);
-  return hipGetLastError();
+  const size_t lds = (size_t)RQ * (D + 4) * 4 + 4 * 32 * 4;   // queries, per-wave norms
+  return dispatch_dt(dt, [&](auto DT) {
+    return launch_lds(score_matrix_kernel<DT()>, grid, 256, lds, s, corpus, N, D, q, Q, norm_mode, out);
+  });
 }
 
 hipError_t rank_of_targets(const float* S, int64_t Q, int64_t N, const int64_t* pq, const int64_t* pt, int64_t T,

@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
   int ptr0 = 0;
   auto put = [&](int rg) {   // candidate rg of the previous tile -> this lane's bucket
     if ((pokm >> rg) & 1u) {
-      const int rr = (rg & 3) + 8 * (rg >> 2) + 4 * h;
+      const int rr = c_row(rg, h);
       const uint64_t e = ((uint64_t)score_key(P[rg], nan_first) << 32) | (uint32_t)~(uint32_t)(ptr0 + rr);
       asm volatile("ds_write_b64 %0, %1" ::"v"(bkt + 512u * bcnt), "v"(e) : "memory");
       ++bcnt;
@@ -365,14 +365,14 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
       const float tf = thr < 0x00800000u ? -INFINITY
                                          : __uint_as_float((thr & 0x80000000u) ? (thr & 0x7fffffffu) : ~thr);
       const int vrows = (int)min((int64_t)32, nrows - tr0);   // valid rows of this tile
-      // the 16 rows' reciprocals: rows (rg & 3) + 8 (rg >> 2) + 4 h are four 16-byte runs
+      // the 16 rows' reciprocals: rows c_row(rg, h) are four 16-byte runs
       f32x4c nv[4];
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4) nv[q4] = *(const f32x4c*)(nrm + 8 * q4 + 4 * h);
       uint32_t okm = 0u;
 #pragma unroll
       for (int rg = 0; rg < 16; ++rg) {
-        const int rr = (rg & 3) + 8 * (rg >> 2) + 4 * h;
+        const int rr = c_row(rg, h);
         const float sc = (acc[rg] + acc2[rg]) * nv[rg >> 2][rg & 3];
         P[rg] = sc;
         okm |= (qvalid && rr < vrows && sc >= tf) ? 1u << rg : 0u;
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
             float sc = P[0];
 #pragma unroll
             for (int rg = 1; rg < 16; ++rg) sc = rg == i ? P[rg] : sc;
-            const int rr = (i & 3) + 8 * (i >> 2) + 4 * h;
+            const int rr = c_row(i, h);
             const uint64_t e = m ? (((uint64_t)score_key(sc, nan_first) << 32) | (uint32_t)~(uint32_t)(tr0 + rr)) : 0ull;
 #pragma unroll
             for (int p = 15; p > 0; --p) L[p] = e > L[p - 1] ? L[p - 1] : (e > L[p] ? e : L[p]);
@@ -444,18 +444,7 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
     lines_publish<NW>(L, smem, wave, lane, q0, Q, kc, r_begin, f);
     return;
   }
-  __syncthreads();   // ring free -> lists
-  uint32_t* Lk = (uint32_t*)smem;
-  int32_t* Li = (int32_t*)(smem + NT * KC * 4);
-#pragma unroll
-  for (int p = 0; p < KC; ++p) {
-    const bool real = L[p] != 0ull;
-    Lk[tid * KC + p] = real ? (uint32_t)(L[p] >> 32) : 0u;
-    Li[tid * KC + p] = real ? (int32_t)~(uint32_t)L[p] : INT_MAX;
-  }
-  __syncthreads();
-  fold_publish<2 * NW>(Lk, Li, KC, q0, Q, kc, r_begin, f);
-  fold_reduce<NT>(smem, f, q0, Q, kc, nan_first, 0, out_s, out_i);
+  fold_tail<NW>(L, smem, q0, Q, kc, nan_first, r_begin, 0, f, out_s, out_i);
 }
 
 }  // namespace

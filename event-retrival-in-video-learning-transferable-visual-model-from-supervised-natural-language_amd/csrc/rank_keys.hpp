@@ -1,6 +1,9 @@
-// Device helpers shared by the rank kernels (rank.hip, rank_mirror.hip):
-// order keys, the row-norm reciprocal, and the data-independent bitonic
-// top-16 list update (see rank.hip's rank_stream comment).
+// Device helpers shared by every rank kernel (rank.hip, rank_filter.hip,
+// rank_mirror.hip, rank_cert.hip): order keys, the row-norm reciprocal, the
+// MFMA C-fragment row map, the data-independent bitonic top-16 list update
+// (see rank.hip's rank_stream comment) and the workgroup / grid merges of the
+// per-lane lists.  The exact-f32 passes over LDS-staged queries built on these
+// are in rank_pass.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,6 +38,10 @@ __device__ __forceinline__ float decode_key(uint32_t bk, int nan_first) {
   if ((bk == 0xFFFFFFFFu && nan_first) || (bk == 0u && !nan_first)) return __uint_as_float(0x7fc00000u);
   return __uint_as_float((bk & 0x80000000u) ? (bk & 0x7fffffffu) : ~bk);
 }
+
+// Row of a 32x32 MFMA C fragment that register rg (0..15) of a lane in half h (lane >> 5) holds;
+// the column is lane & 31.
+__device__ __forceinline__ constexpr int c_row(int rg, int h) { return (rg & 3) + 8 * (rg >> 2) + 4 * h; }
 
 template <typename I>
 __device__ __forceinline__ bool better(uint32_t ka, I ia, uint32_t kb, I ib) {
@@ -242,6 +249,28 @@ struct FoldWs {
   int ngrp;
 };
 
+// One step of merging a query's NL sorted (key, idx) lists in LDS (list l of query tid: lane
+// (l >> 1) * 64 + (l & 1) * 32 + tid, KC entries, idx INT_MAX = none): the best remaining head
+// into (bk, bi), its list advanced; bi == INT_MAX when every list is exhausted.
+template <int NL>
+__device__ __forceinline__ void lists_pop(const uint32_t* Lk, const int32_t* Li, int KC, int tid, int (&pos)[NL],
+                                          uint32_t& bk, int32_t& bi) {
+  bk = 0u;
+  bi = INT_MAX;
+  int bl = 0;
+#pragma unroll
+  for (int l = 0; l < NL; ++l) {
+    const int src = (l >> 1) * 64 + (l & 1) * 32 + tid;
+    if (pos[l] < KC) {
+      const uint32_t kk = Lk[src * KC + pos[l]];
+      const int32_t ii = Li[src * KC + pos[l]];
+      if (better(kk, ii, bk, bi)) { bk = kk; bi = ii; bl = l; }
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < NL; ++l) pos[l] += (l == bl) ? 1 : 0;
+}
+
 template <int NL>
 __device__ __forceinline__ void fold_publish(const uint32_t* Lk, const int32_t* Li, int KC, int64_t q0, int64_t Q,
                                              int k, int64_t r_begin, const FoldWs& f) {
@@ -256,20 +285,9 @@ __device__ __forceinline__ void fold_publish(const uint32_t* Lk, const int32_t* 
     for (int o = 0; o < 16; ++o) {
       uint64_t e = 0ull;
       if (o < k) {
-        uint32_t bk = 0u;
-        int32_t bi = INT_MAX;
-        int bl = 0;
-#pragma unroll
-        for (int l = 0; l < NL; ++l) {
-          const int src = (l >> 1) * 64 + (l & 1) * 32 + tid;
-          if (pos[l] < KC) {
-            const uint32_t kk = Lk[src * KC + pos[l]];
-            const int32_t ii = Li[src * KC + pos[l]];
-            if (better(kk, ii, bk, bi)) { bk = kk; bi = ii; bl = l; }
-          }
-        }
-#pragma unroll
-        for (int l = 0; l < NL; ++l) pos[l] += (l == bl) ? 1 : 0;
+        uint32_t bk;
+        int32_t bi;
+        lists_pop<NL>(Lk, Li, KC, tid, pos, bk, bi);
         if (bi != INT_MAX) {
           e = ((uint64_t)bk << 32) | (uint32_t)~(uint32_t)(r_begin + bi);
           if (o == k - 1) { kth = bk; full = true; }
@@ -438,13 +456,39 @@ __device__ __forceinline__ void fold_reduce(char* smem, const FoldWs& f, int64_t
   if (stamp && tid == 0) stamp[8] = __builtin_amdgcn_s_memrealtime();
 }
 
+// The in-launch merge as the tail of a pass with NW waves (every thread calls it, its loads and
+// LDS traffic drained): the packed lists L spilled to LDS as (key, idx) lists over the pass's
+// query / ring area, then fold_publish and fold_reduce.  stamp (nullable): rank_reg's timing probe.
+template <int NW>
+__device__ __forceinline__ void fold_tail(const uint64_t (&L)[16], char* smem, int64_t q0, int64_t Q, int k,
+                                          int nan_first, int64_t r_begin, int64_t index_base, const FoldWs& f,
+                                          float* __restrict__ out_s, int64_t* __restrict__ out_i,
+                                          unsigned long long* stamp = nullptr) {
+  constexpr int NT = 64 * NW, KC = 16;
+  const int tid = threadIdx.x;
+  __syncthreads();   // query area / ring free -> lists
+  if (stamp && tid == 0) stamp[2] = __builtin_amdgcn_s_memrealtime();
+  uint32_t* Lk = (uint32_t*)smem;
+  int32_t* Li = (int32_t*)(smem + NT * KC * 4);
+#pragma unroll
+  for (int p = 0; p < KC; ++p) {
+    const bool real = L[p] != 0ull;
+    Lk[tid * KC + p] = real ? (uint32_t)(L[p] >> 32) : 0u;
+    Li[tid * KC + p] = real ? (int32_t)~(uint32_t)L[p] : INT_MAX;
+  }
+  __syncthreads();
+  fold_publish<2 * NW>(Lk, Li, KC, q0, Q, k, r_begin, f);
+  if (stamp && tid == 0) stamp[3] = __builtin_amdgcn_s_memrealtime();
+  fold_reduce<NT>(smem, f, q0, Q, k, nan_first, index_base, out_s, out_i, stamp);
+}
 
 // ---- split merge (round 5): the pass publishes its workgroup's top-k, a second launch merges.
 // The in-launch merge above chains global round trips after the stream (a ticket, the group
 // reducer's slab lines, a second ticket, the final reducer: ~60-90 us at 125k-1M rows,
 // scripts/rank_stamp.py), and its fold_publish merged the 8 lists of a query with one thread
 // per query (~10-20 us).  Here each query's 8 lists (4 waves x 2 lane halves) merge as a tree:
-// the two halves by shuffles (merge16_desc), then wave 0 folds the other waves' lists from LDS;
+// the two halves by shuffles (merge16_desc), then wave 0 folds the other waves' lists from LDS
+// (workgroup_merge16, which the filtered stream's tail shares);
 // the workgroup's top-k goes to its slab line (rows global) and raises gtau[q] to its k-th key.
 // fold_merge_kernel (rank.hip) then reduces each query's nwg lines in one workgroup.
 // smem: >= 4 waves x 32 queries x 16 entries x 8 B = 16 KB, free (the caller's ring, after the
@@ -460,18 +504,14 @@ __device__ __forceinline__ void merge16_xor(uint64_t (&L)[16], int off) {
   merge16_desc(L, c);
 }
 
+// The wave tree: a query's 2 NW lists merged into lane r = query r of wave 0, for which it returns
+// true.  smem: [NW][32][16] u64 over the caller's query / ring area (its first barrier frees it).
 template <int NW>
-__device__ __forceinline__ void lines_publish(uint64_t (&L)[16], char* smem, int wave, int lane, int64_t q0, int64_t Q,
-                                              int k, int64_t r_begin, const FoldWs& f) {
+__device__ __forceinline__ bool workgroup_merge16(uint64_t (&L)[16], char* smem, int wave, int lane) {
   const int r = lane & 31;
-#pragma unroll
-  for (int p = 0; p < 16; ++p) {   // rows relative to the workgroup's range -> global (same order)
-    const uint64_t e = L[p];
-    L[p] = e ? ((e & 0xffffffff00000000ull) | (uint32_t)~(uint32_t)(r_begin + (int64_t)~(uint32_t)e)) : 0ull;
-  }
   merge16_xor(L, 32);              // the wave's two half-lists of query r (both halves get it)
   uint64_t* wl = (uint64_t*)smem;  // [NW][32][16]
-  __syncthreads();                 // every wave is done with its ring slots
+  __syncthreads();                 // every wave is done with its ring slots / the queries
   if (wave > 0 && lane < 32) {
 #pragma unroll
     for (int p = 0; p < 16; ++p) wl[((wave * 32) + r) * 16 + p] = L[p];
@@ -485,6 +525,21 @@ __device__ __forceinline__ void lines_publish(uint64_t (&L)[16], char* smem, int
       for (int p = 0; p < 16; ++p) c[p] = wl[((w * 32) + r) * 16 + p];
       merge16_desc(L, c);
     }
+    return true;
+  }
+  return false;
+}
+
+template <int NW>
+__device__ __forceinline__ void lines_publish(uint64_t (&L)[16], char* smem, int wave, int lane, int64_t q0, int64_t Q,
+                                              int k, int64_t r_begin, const FoldWs& f) {
+  const int r = lane & 31;
+#pragma unroll
+  for (int p = 0; p < 16; ++p) {   // rows relative to the workgroup's range -> global (same order)
+    const uint64_t e = L[p];
+    L[p] = e ? ((e & 0xffffffff00000000ull) | (uint32_t)~(uint32_t)(r_begin + (int64_t)~(uint32_t)e)) : 0ull;
+  }
+  if (workgroup_merge16<NW>(L, smem, wave, lane)) {
     if (q0 + r < Q) {
       typedef unsigned int u32x4lp __attribute__((ext_vector_type(4)));
       u32x4lp* dst = (u32x4lp*)(f.slab + ((int64_t)RB * f.Qpad + q0 + r) * 16);

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void rank_mirror_kernel(const uint16_t* __rest
                                                           const float* __restrict__ queries, int64_t Q, int k,
                                                           int64_t rows_per_wg, int nan_first, FoldWs f,
                                                           float* __restrict__ out_s, int64_t* __restrict__ out_i) {
-  constexpr int NW = 4, NT = 64 * NW, KC = 16, NCH = D / 64, NS = D / 16;
+  constexpr int NW = 4, KC = 16, NCH = D / 64, NS = D / 16;
   constexpr int SLOT = 32 * 128;   // 32 rows x 64 k fp16
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem;   // [NW][NB][SLOT]
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void rank_mirror_kernel(const uint16_t* __rest
       uint32_t okm = 0u;
 #pragma unroll
       for (int rg = 0; rg < 16; ++rg) {
-        const int rr = (rg & 3) + 8 * (rg >> 2) + 4 * h;
+        const int rr = c_row(rg, h);
         const int64_t gr = (int64_t)tr0 + rr;   // relative to r_begin
         const uint32_t key = score_key(acc[rg], nan_first);
         const bool ok = qvalid && gr < nrows && key >= thr;
@@ -257,18 +257,7 @@ __global__ __launch_bounds__(256) void rank_mirror_kernel(const uint16_t* __rest
     lines_publish<NW>(L, smem, wave, lane, q0, Q, k, r_begin, f);
     return;
   }
-  __syncthreads();   // ring free -> lists
-  uint32_t* Lk = (uint32_t*)smem;
-  int32_t* Li = (int32_t*)(smem + NT * KC * 4);
-#pragma unroll
-  for (int p = 0; p < KC; ++p) {
-    const bool real = L[p] != 0ull;
-    Lk[tid * KC + p] = real ? (uint32_t)(L[p] >> 32) : 0u;
-    Li[tid * KC + p] = real ? (int32_t)~(uint32_t)L[p] : INT_MAX;
-  }
-  __syncthreads();
-  fold_publish<2 * NW>(Lk, Li, KC, q0, Q, k, r_begin, f);
-  fold_reduce<NT>(smem, f, q0, Q, k, nan_first, 0, out_s, out_i);
+  fold_tail<NW>(L, smem, q0, Q, k, nan_first, r_begin, 0, f, out_s, out_i);
 }
 
 // ---- exact re-score of each query's kc mirror candidates (one wave per query)
@@ -327,7 +316,7 @@ __global__ __launch_bounds__(64) void mirror_rescore_kernel(const void* __restri
   if (r == 0) {
 #pragma unroll
     for (int rg = 0; rg < 16; ++rg) {
-      const int rr = (rg & 3) + 8 * (rg >> 2) + 4 * h;
+      const int rr = c_row(rg, h);
       sc[rr] = acc[rg] * nrm[rr];
     }
   }

@@ -7,7 +7,7 @@ one shape, ONE process, interleaved rounds, HIP events on the launch stream.
 
 Shape: rows x 512 f32 (default 1M), Q = 32, k = 10.  Cases:
   a_topk          mi_rank_topk as the product runs it (certified pass + gated exact pass here)
-  stream          mi_rank_topk through rank_stream, the kernel the filtered pass derives from
+  stream          mi_rank_topk through rank_stream, the kernel the filtered pass shares its body with
                   (A/B build: MICLIP_RANK_REG=0)
   b_all           filtered, no mask and no range: everything visible
   c_range_eighth  filtered, every query ranged to the same eighth of the rows

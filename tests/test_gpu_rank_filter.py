@@ -294,6 +294,81 @@ def test_two_thousand_identical_visible_rows(gpu, k):
     assert torch.equal(got[1][0], first) and torch.equal(got[1][1], first)
 
 
+# ------------------------------------------------------------------ against the NumPy oracle
+# The bitwise tests above compare the filtered pass with rank_topk, which at D != 512 or k > 16
+# runs the same pass body under the other row policy; this one compares it with float64 NumPy.
+def _small_ranges(N):
+    """_mid_ranges' pattern at N = 1000 (three 384-row workgroups)."""
+    r = [[0, N]] * 33
+    r[0] = [33, 95]              # starts and ends mid-tile
+    r[1] = [700, 701]            # one row
+    r[2] = [900, 900]            # begin == end
+    r[3] = [240, 220]            # begin > end
+    r[4] = [N - 10, N + 500]     # past N
+    r[5] = [N, N + 10]           # wholly past N
+    r[6] = [-50, 7]              # clipped at 0
+    r[7] = [767, 769]            # across a workgroup edge
+    r[8] = [800, 805]            # fewer than k rows
+    for i in range(9, 32):       # differing ranges inside one 32-query block
+        r[i] = [30 * i, 30 * i + 80 + 13 * i]
+    r[32] = [800, 900]           # the second query block's hull: two workgroups without a live tile
+    return r
+
+
+ORACLE_ZERO_VISIBLE, ORACLE_ZERO_HIDDEN = 750, 100
+
+
+@pytest.fixture(scope="module", params=[32, 96])
+def oracle_case(gpu, request):
+    """1000 x D f32 rows, 33 queries, a mask of rows 40-45 and 700-990, per-query ranges, a visible
+    and a hidden zero row; per query the visible rows and their float64 scores (computed once)."""
+    import torch
+    from oracle import rank_ref
+    D, N = request.param, 1000
+    corpus = _rows(gpu, N, D, torch.float32, seed=50 + D).clone()
+    corpus[[ORACLE_ZERO_VISIBLE, ORACLE_ZERO_HIDDEN]] = 0.0
+    q = _queries(gpu, 33, D, seed=51)
+    mask = torch.zeros(N, dtype=torch.bool, device=gpu)
+    mask[40:46] = True
+    mask[700:991] = True
+    ranges = _small_ranges(N)
+    c, qq, m = corpus.cpu().numpy(), q.cpu().numpy(), mask.cpu().numpy()
+    ref = []
+    for qi, (b, e) in enumerate(ranges):
+        b, e = max(b, 0), min(e, N)
+        vis = np.arange(b, e)[m[b:e]] if b < e else np.zeros(0, np.int64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            S = rank_ref.scores_ref(c[vis], qq[qi:qi + 1])[0] if len(vis) else np.zeros(0)
+        ref.append((vis, S))
+    return corpus, q, mask, ranges, ref
+
+
+@pytest.mark.parametrize("nan", ["first", "last"])
+@pytest.mark.parametrize("k", [10, 17])
+def test_filtered_matches_oracle(oracle_case, k, nan):
+    """rank_topk_filtered (k = 10: the stream kernel, k = 17: the tiles kernel; D = 32 / 96: 1 / 3
+    chunks per tile) against NumPy over each query's gathered visible rows, indices mapped back."""
+    from oracle import rank_ref
+    corpus, q, mask, ranges, ref = oracle_case
+    gs, gi = _filtered(corpus, q, k, mask=mask, ranges=ranges, nan=nan)
+    gs, gi = gs.cpu().numpy(), gi.cpu().numpy()
+    assert gs.shape == (33, k) and gi.shape == (33, k)
+    empty = 0
+    for qi, (vis, S) in enumerate(ref):
+        kk = min(k, len(vis))
+        assert (gi[qi, kk:] == -1).all() and (gs[qi, kk:] == NEG_INF).all(), qi
+        empty += kk == 0
+        if kk == 0:
+            continue
+        assert np.isin(gi[qi, :kk], vis).all(), (qi, gi[qi, :kk])            # only visible rows
+        pos = np.searchsorted(vis, gi[qi, :kk])                              # global row -> gathered position
+        rank_ref.assert_topk_equivalent(gs[qi, :kk], pos, S, k, nan_policy=nan)
+    assert empty >= 4                                                        # r[2], r[3], r[5], r[6]
+    assert ranges[20][0] <= ORACLE_ZERO_VISIBLE < ranges[20][1]             # [600, 940): more than k visible rows
+    assert (ORACLE_ZERO_VISIBLE in gi[20]) == (nan == "first")
+    assert not (gi == ORACLE_ZERO_HIDDEN).any()
+
+
 # ------------------------------------------------------------------ library
 @pytest.fixture(scope="module")
 def library(gpu):
