@@ -38,8 +38,7 @@
 // activation fragment) so each lane holds 4 consecutive output columns of one
 // row: 8-byte (bf16) / 16-byte (f32) stores, a wave writing whole 128/256-byte
 // row segments over its 4 column fragments.
-#include "common.hpp"
-#include "internal.hpp"
+#include "gemm_common.hpp"
 
 namespace miclip {
 
@@ -55,72 +54,20 @@ static_assert((LEAD - 1) * STAGE_OPS + 16 <= VM_MAX, "counted waits exceed vmcnt
 constexpr int MAX_N = 4096;  // bias staged in LDS
 constexpr int EPI_NONE = 9;  // timing probe (variant 8): main loop only
 
-// QuickGELU x * sigmoid(1.702 x) with the hardware exp/rcp (~1 ulp; output is bf16)
-__device__ __forceinline__ float quick_gelu(float v) {
-  return v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v));
-}
-
-__device__ __forceinline__ int swz(int x) { return (0x1320 >> (4 * x)) & 0xF; }  // g = {0,2,3,1}
-
-// LDS read the compiler does not see: a plain ds_read of the bias would make
-// hipcc wait vmcnt(0) (it cannot prove the read misses the in-flight LDS-DMA
-// of the next tile's stages), draining the prefetch at every epilogue.
-__device__ __forceinline__ float4 lds_read_f4(const float* p) {
-  float4 v;
-  const uint32_t addr = (uint32_t)(uintptr_t)(const LDS_AS float*)p;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-
-// Logical tile t -> (m-block, n-block).  Tiles are taken in groups of `ng`
-// n-blocks (ng >= tiles_n: plain m-major raster): within a group all m-blocks
-// are swept with the group's n-blocks innermost, so the W column panel of the
-// group stays L2-resident while the XCD streams A (each A panel is re-read by
-// the ng concurrent tiles of its row).  With xcd_remap each XCD owns a
-// contiguous run of t, i.e. one group and a contiguous range of m-blocks.
-__device__ __forceinline__ void tile_coords(int t, int tiles_m, int tiles_n, int ng, int& mb, int& nb) {
-  if (ng <= 0 || ng >= tiles_n) {
-    mb = t / tiles_n;
-    nb = t % tiles_n;
-    return;
-  }
-  const int per = tiles_m * ng;
-  const int g = t / per, r = t - g * per;
-  const int ngg = min(ng, tiles_n - g * ng);
-  mb = r / ngg;
-  nb = g * ng + r % ngg;
-}
-
-template <bool V>
-struct BoolT {};
-
 // EPI_SPLIT_GELU (split-f16 GEMM, fp32 tower c_fc): QuickGELU of the f32 pre-activations v
 // (columns n .. n + 3 of row m; the f32 epilogue's expf form) scaled by the row's power of two
 // and split into the next GEMM's operand [y1 | y1 | y2] (precise.hip split2h_rows, role 0).  The
 // scale comes from a bound instead of the row's max, which this tile cannot see:
 // |y| <= |v| <= max|a_m| * max_n sum_k |W_nk| + max|b| (with 2^-8 of slack for the f32 rounding
 // of v), so |y s| < 2^14 (1 + 2^-8); a loose bound only lowers the subnormal floor's share.
-__device__ __forceinline__ int split_exp_g(float mx) {
-  if (!(mx > 0.f) || !__builtin_isfinite(mx)) return 0;
-  int ex;
-  (void)frexpf(mx, &ex);
-  const int e = 14 - ex;
-  return e > 126 ? 126 : (e < -126 ? -126 : e);
-}
 __device__ __forceinline__ void split_gelu_store(const GemmArgs& a, int m, int n, float4 v) {
   const float bound = (a.rmax[m] * a.bnd_w + a.bnd_b) * (1.0f + 0.00390625f);
-  const int e = split_exp_g(bound);
-  const float y[4] = {v.x * (1.0f / (1.0f + expf(-1.702f * v.x))), v.y * (1.0f / (1.0f + expf(-1.702f * v.y))),
-                      v.z * (1.0f / (1.0f + expf(-1.702f * v.z))), v.w * (1.0f / (1.0f + expf(-1.702f * v.w)))};
+  const int e = split_exp(bound);
+  const float y[4] = {quick_gelu_f32(v.x), quick_gelu_f32(v.y), quick_gelu_f32(v.z), quick_gelu_f32(v.w)};
   typedef _Float16 h4 __attribute__((ext_vector_type(4)));
   _Float16 p1[4], p2[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float ys = ldexpf(y[i], e);
-    p1[i] = (_Float16)ys;
-    const float f1 = (float)p1[i];
-    p2[i] = __builtin_isfinite(f1) ? (_Float16)(ys - f1) : (_Float16)0.f;
-  }
+  for (int i = 0; i < 4; ++i) split2h(ldexpf(y[i], e), p1[i], p2[i]);
   const h4 h1 = {p1[0], p1[1], p1[2], p1[3]}, h2 = {p2[0], p2[1], p2[2], p2[3]};
   _Float16* o = (_Float16*)a.out + (int64_t)m * a.ldo + n;
   const int N = a.N;
@@ -129,13 +76,12 @@ __device__ __forceinline__ void split_gelu_store(const GemmArgs& a, int m, int n
   *(h4*)(o + 2 * N) = h2;
   if (n == 0) a.rsc_out[m] = ldexpf(1.f, -e);
 }
-typedef _Float16 f16x8_g __attribute__((ext_vector_type(8)));
 // one 16x16x32 MFMA on bf16 or (split-f16 operands) fp16 fragments of the same bytes
-__device__ __forceinline__ f32x4 mfma16(BoolT<false>, bf16x8 b, bf16x8 a, f32x4 c) {
+__device__ __forceinline__ f32x4 mfma16(std::bool_constant<false>, bf16x8 b, bf16x8 a, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, c, 0, 0, 0);
 }
-__device__ __forceinline__ f32x4 mfma16(BoolT<true>, bf16x8 b, bf16x8 a, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_g, b), __builtin_bit_cast(f16x8_g, a), c, 0, 0, 0);
+__device__ __forceinline__ f32x4 mfma16(std::bool_constant<true>, bf16x8 b, bf16x8 a, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, b), __builtin_bit_cast(f16x8, a), c, 0, 0, 0);
 }
 
 template <int N>
@@ -243,7 +189,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_kernel(GemmArgs a
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = mfma16(BoolT<F16>{}, bfr[ni], af[mi], acc[mi][ni]);
+          acc[mi][ni] = mfma16(std::bool_constant<F16>{}, bfr[ni], af[mi], acc[mi][ni]);
     }
 
     // ---------------------------------------------------------- epilogue
@@ -405,7 +351,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs a) {
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni)
-        acc[mbase + mi][ni] = mfma16(BoolT<F16>{}, bfr[ni], af[(mbase % (8 / CL)) + mi], acc[mbase + mi][ni]);
+        acc[mbase + mi][ni] = mfma16(std::bool_constant<F16>{}, bfr[ni], af[(mbase % (8 / CL)) + mi], acc[mbase + mi][ni]);
     if (PRIO) __builtin_amdgcn_s_setprio(0);
     (void)count;
   };
@@ -949,151 +895,125 @@ int n_group(int tiles_n, int K) {
   return 0;
 }
 
+// The generic tiled kernel, the path of every shape and variant the staged kernels do not take:
+// 256 x 256 tiles on big shapes, 128 x 128 otherwise, persistent grids.
+template <int EPI, bool F16 = false>
+hipError_t launch_tiled(const GemmArgs& a, bool big, hipStream_t s) {
+  const int cus = cu_count();
+  if (big) return launch_kernel(gemm_kernel<EPI, 256, 256, 2, 4, F16>, persistent_grid(tile_count(a, 256, 256), cus), 512, s, a);
+  return launch_kernel(gemm_kernel<EPI, 128, 128, 2, 2, F16>, persistent_grid(tile_count(a, 128, 128), 2 * cus), 256, s, a);
+}
+
 #if MICLIP_AB
 // A/B build (scripts/ab, MICLIP_AB=1): every schedule, ablation and probe
-// variant of rounds 1-2 stays selectable by GemmArgs::variant for
+// variant of rounds 1-2 stays selectable by GemmArgs::variant (!= 0 here; launch takes 0) for
 // scripts/gemm_micro.py and the bit-identity tests; the product library
-// (MICLIP_AB=0) compiles only the default path below.
+// (MICLIP_AB=0) compiles only the default path below.  A variant whose kernel does not apply to
+// the shape or epilogue takes the generic tiled kernel, except where a case says otherwise.
 template <int EPI>
 hipError_t launch_ab(const GemmArgs& a, hipStream_t s) {
   const bool big = a.N % 256 == 0 && a.M >= 1024;
-  // variant 0 (default): ping-pong, one 32-MFMA cluster per stage, direct
-  // permlane-swapped row stores for bf16 outputs (16, or its persistent form
-  // 18 on wide N) / LDS-staged rows for f32 (3) (scripts/gemm_micro.py);
-  // 1 = persistent ring; 8 = main-loop-only timing probe (no epilogue).
   const bool bf16_out = EPI == EPI_BF16 || EPI == EPI_GELU_BF16;
-  // default for bf16 outputs: the persistent ping-pong (18) on wide GEMMs (N >= 2048:
-  // qkv, c_fc; +1.7-3 % in scripts/gemm_micro.py) and on K <= 1024 (out_proj),
-  // the one-tile-per-workgroup ping-pong (16) on N = 768 with long K (c_proj:
-  // the persistent kernel's static tile split loses 3.8 % there against the
-  // dispatcher's dynamic one)
-  if (a.patch_R) {  // fused patch gather: f32 output rows, ping-pong only
-    if (!big || a.K != 3 * 32 * 32 || (a.patch_R & 31)) return hipErrorInvalidValue;
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    hipLaunchKernelGGL((gemm_pp_kernel<EPI, 1, false, false, false, true>), dim3(nt), dim3(512), 0, s, a);
-    return hipGetLastError();
+  const bool staged = big && a.K / BK >= LEAD;               // the ping-pong kernels' shapes
+  const bool persist = staged && bf16_out && !a.group;       // the persistent ping-pong kernel's
+  const int cus = cu_count();
+  const int nt = tile_count(a, 256, 256);
+  auto pp = [&](auto kernel, const GemmArgs& ga) { return launch_kernel(kernel, nt, 512, s, ga); };
+  auto ppp = [&](auto kernel, const GemmArgs& ga) { return launch_kernel(kernel, persistent_grid(nt, cus), 512, s, ga); };
+  GemmArgs ga = a;   // a with the tile-order group width some variants set
+  for (int v = a.variant;;) {
+    switch (v) {
+      case 1:   // persistent ring: the generic tiled kernel
+        break;
+      case 2:   // ping-pong, two 16-MFMA clusters per stage, LDS-staged output rows
+        if (staged) return pp(gemm_pp_kernel<EPI, 2, false>, ga);
+        break;
+      case 3:   // ping-pong, one 32-MFMA cluster per stage, LDS-staged output rows
+        if (staged) return pp(gemm_pp_kernel<EPI, 1, false>, ga);
+        break;
+      case 4:   // 2 with the MFMA clusters at raised priority
+        if (staged) return pp(gemm_pp_kernel<EPI, 2, true>, ga);
+        break;
+      case 5:   // 3 with the MFMA clusters at raised priority
+        if (staged) return pp(gemm_pp_kernel<EPI, 1, true>, ga);
+        break;
+      case 6:   // 3 with the grouped (L2-resident W panel) tile order
+        ga.ngroup = n_group(a.N / 256, a.K);
+        v = 3;
+        continue;
+      case 8:   // main-loop-only timing probe (no epilogue)
+        if (staged) return pp(gemm_pp_kernel<EPI_NONE, 1, false>, a);
+        break;
+      case 16:   // ping-pong, direct permlane-swapped row stores (bf16 outputs; 3 for f32 outputs)
+        if (staged && bf16_out) return pp(gemm_pp_kernel<EPI, 1, false, true>, a);
+        v = 3;
+        continue;
+      case 17:   // experiment: 16 with non-temporal output stores
+        if (staged && bf16_out) return pp(gemm_pp_kernel<EPI, 1, false, true, true>, a);
+        break;
+      case 18:   // persistent ping-pong
+        if (persist) return ppp(gemm_ppp_kernel<EPI>, a);
+        break;
+      case 19:   // persistent + timing probe
+        if (persist) return ppp(gemm_ppp_kernel<EPI, true>, a);
+        break;
+      case 20:   // persistent, early group-0 epilogue
+        if (persist) return ppp(gemm_ppp_kernel<EPI, false, true>, a);
+        break;
+      case 31 ... 33:   // main-loop ablation probes: no DMA / no fragment reads / no MFMAs
+        if (staged) return pp(v == 31 ? gemm_abl_kernel<1> : v == 32 ? gemm_abl_kernel<2> : gemm_abl_kernel<3>, a);
+        break;
+      case 34 ... 35:   // full-line fetch probes
+        if (staged && (a.K / BK) % 2 == 0) return pp(v == 34 ? gemm_abl_kernel<4> : gemm_abl_kernel<5>, a);
+        break;
+      case 40 ... 59:   // tile-order probe: the persistent kernel with n-blocks walked in groups of (v - 40)
+        ga.ngroup = v - 40;
+        if (persist) return ppp(gemm_ppp_kernel<EPI>, ga);
+        break;
+      case 60 ... 69:   // persistent kernel, non-temporal output stores, n-blocks in groups of (v - 60)
+        ga.ngroup = v - 60;
+        if (persist) return ppp(gemm_ppp_kernel<EPI, false, false, true>, ga);
+        break;
+      case 70:   // one wave per SIMD, BK 64 (gemm_w4.hip)
+        if (bf16_out && gemm_w4_ok(a)) return gemm_w4(a, EPI, s, cus);
+        break;
+      case 80 ... 86:
+      case 89:   // 8-phase interleave (gemm_8p.hip); n-groups of (v - 80)
+        ga.ngroup = v - 80;
+        if (bf16_out && gemm_8p_ok(a)) return gemm_8p(ga, EPI, s, cus);
+        break;
+      case 87 ... 88:   // 8-phase probes 7, 8 (gemm_8p.hip ABL)
+        if (bf16_out && gemm_8p_ok(a)) return gemm_8p(a, EPI, s, cus, v - 80);
+        break;
+      case 91 ... 94:
+      case 96:   // 8-phase probes 1-4, 6
+        if (bf16_out && gemm_8p_ok(a)) return gemm_8p(a, EPI, s, cus, v - 90);
+        break;
+      case 97 ... 99:   // 8-phase: 97 aligned epilogue, 98 early phase-1 DMAs (+0-3 % over 80), 99 both
+        if (bf16_out && gemm_8p_ok(a)) return gemm_8p(a, EPI, s, cus, v + 3);   // gemm_8p's 100, 101, 102
+        break;
+      case 110 ... 119:   // 8-phase, second schedule (gemm_8q.hip), mode v - 110; 98 where it does not apply
+        if (!bf16_out) break;
+        if (gemm_8q_ok(a)) return gemm_8q(a, EPI, s, cus, v - 110);
+        v = 98;
+        continue;
+      case 120 ... 124:   // 256 x 128 tiles, deferred epilogue (gemm_8r.hip), mode v - 120; 98 where it does not apply
+        if (!bf16_out) break;
+        if (gemm_8r_ok(a)) return gemm_8r(a, EPI, s, cus, v - 120);
+        v = 98;
+        continue;
+      case 125:   // gemm_8q with whole-row epilogue stores
+        if (bf16_out && gemm_8q_ok(a)) return gemm_8q(a, EPI, s, cus, 10);
+        break;
+      case 131 ... 139:   // gemm_8q, n-tiles in groups of (v - 130); 131: m-major raster
+        ga.ngroup = v == 131 ? -1 : v - 130;
+        if (bf16_out && gemm_8q_ok(a)) return gemm_8q(ga, EPI, s, cus, 0);
+        break;
+      default:
+        break;
+    }
+    return launch_tiled<EPI>(a, big, s);
   }
-  // (N = 768: persistent on K = 768 since the stage streaming, +5 % on out500;
-  // c_proj, K = 3072, stays one tile per workgroup: -3.8 % persistent)
-  int v = a.variant == 0 ? (bf16_out ? ((a.N >= 2048 || a.K <= 1024) && !a.group ? 18 : 16) : 3) : a.variant;
-  // default for bf16 outputs since the 8-phase kernel (gemm_8p.hip): +12-18 % over 16/18 on all four
-  // B/32 tower shapes at M = 500k, bit-identical (scripts/gemm_micro.py); 16/18 stay for K % 128 != 0 / grouped rows
-  if (a.variant == 0 && bf16_out && gemm_8p_ok(a)) v = 98;   // (+ early phase-1 DMAs: 0-3 % over 80)
-  // default since gemm_8q.hip (descriptor DMAs, template-form waits, descriptor-store epilogue):
-  // fc500 -4..-7 %, qkv500 -3..-4 %, proj500 -6 %, out500 +-3 % against v98, bit-identical
-  if (a.variant == 0 && bf16_out && gemm_8q_ok(a)) v = 110;
-  if (v == 16 && !bf16_out) v = 3;
-  if (big && v == 16 && a.K / BK >= LEAD) {
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    hipLaunchKernelGGL((gemm_pp_kernel<EPI, 1, false, true>), dim3(nt), dim3(512), 0, s, a);
-    return hipGetLastError();
-  }
-  if (v >= 131 && v <= 139 && bf16_out && gemm_8q_ok(a)) {   // 8-phase, n-tiles in groups of (v - 130); 131: raster
-    GemmArgs ga = a;
-    ga.ngroup = v == 131 ? -1 : v - 130;
-    return gemm_8q(ga, EPI, s, cu_count(), 0);
-  }
-  if (v == 125 && bf16_out && gemm_8q_ok(a)) return gemm_8q(a, EPI, s, cu_count(), 10);   // whole-row epilogue stores
-  if (v >= 120 && v <= 124 && bf16_out) {   // 256 x 128 tiles, deferred epilogue (v98 where it does not apply)
-    if (gemm_8r_ok(a)) return gemm_8r(a, EPI, s, cu_count(), v - 120);
-    v = 98;
-  }
-  if (v >= 110 && v <= 119 && bf16_out) {   // 8-phase, second schedule (gemm_8p's v98 where it does not apply)
-    if (gemm_8q_ok(a)) return gemm_8q(a, EPI, s, cu_count(), v - 110);
-    v = 98;
-  }
-  if (v == 70 && bf16_out && gemm_w4_ok(a)) return gemm_w4(a, EPI, s, cu_count());   // one wave per SIMD, BK 64
-  if (((v >= 91 && v <= 96 && v != 95) || v == 87 || v == 88) && bf16_out && gemm_8p_ok(a)) return gemm_8p(a, EPI, s, cu_count(), v < 90 ? v - 80 : v - 90);   // 8-phase probes
-  if (v == 97 && bf16_out && gemm_8p_ok(a)) return gemm_8p(a, EPI, s, cu_count(), 100);   // 8-phase, aligned epilogue
-  if (v == 98 && bf16_out && gemm_8p_ok(a)) return gemm_8p(a, EPI, s, cu_count(), 101);   // 8-phase, early phase-1 DMAs
-  if (v == 99 && bf16_out && gemm_8p_ok(a)) return gemm_8p(a, EPI, s, cu_count(), 102);   // both
-  if (v >= 80 && v < 90 && bf16_out && gemm_8p_ok(a)) {   // 8-phase interleave; n-groups of (v - 80)
-    GemmArgs ga = a;
-    ga.ngroup = v - 80;
-    return gemm_8p(ga, EPI, s, cu_count());
-  }
-  if (big && v >= 60 && v < 70 && bf16_out && a.K / BK >= LEAD && !a.group) {
-    // persistent kernel, non-temporal output stores, n-blocks in groups of (v - 60)
-    GemmArgs ga = a;
-    ga.ngroup = v - 60;
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    const int grid = nt < cu_count() ? nt : cu_count();
-    hipLaunchKernelGGL((gemm_ppp_kernel<EPI, false, false, true>), dim3(grid), dim3(512), 0, s, ga);
-    return hipGetLastError();
-  }
-  if (big && v >= 40 && v < 60 && bf16_out && a.K / BK >= LEAD && !a.group) {
-    // tile-order probe: the persistent kernel with n-blocks walked in groups of (v - 40)
-    GemmArgs ga = a;
-    ga.ngroup = v - 40;
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    const int grid = nt < cu_count() ? nt : cu_count();
-    hipLaunchKernelGGL((gemm_ppp_kernel<EPI>), dim3(grid), dim3(512), 0, s, ga);
-    return hipGetLastError();
-  }
-  if (big && v == 18 && bf16_out && a.K / BK >= LEAD && !a.group) {  // persistent ping-pong
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    const int grid = nt < cu_count() ? nt : cu_count();
-    hipLaunchKernelGGL((gemm_ppp_kernel<EPI>), dim3(grid), dim3(512), 0, s, a);
-    return hipGetLastError();
-  }
-  if (big && v == 20 && bf16_out && a.K / BK >= LEAD && !a.group) {  // persistent, early group-0 epilogue
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    const int grid = nt < cu_count() ? nt : cu_count();
-    hipLaunchKernelGGL((gemm_ppp_kernel<EPI, false, true>), dim3(grid), dim3(512), 0, s, a);
-    return hipGetLastError();
-  }
-  if (big && v == 19 && bf16_out && a.K / BK >= LEAD && !a.group) {  // persistent + timing probe
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    const int grid = nt < cu_count() ? nt : cu_count();
-    hipLaunchKernelGGL((gemm_ppp_kernel<EPI, true>), dim3(grid), dim3(512), 0, s, a);
-    return hipGetLastError();
-  }
-  if (big && v == 17 && bf16_out && a.K / BK >= LEAD) {  // experiment: non-temporal output stores
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    hipLaunchKernelGGL((gemm_pp_kernel<EPI, 1, false, true, true>), dim3(nt), dim3(512), 0, s, a);
-    return hipGetLastError();
-  }
-  if (big && v >= 31 && v <= 33 && a.K / BK >= LEAD) {  // main-loop ablation probes
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    if (v == 31) hipLaunchKernelGGL(gemm_abl_kernel<1>, dim3(nt), dim3(512), 0, s, a);
-    else if (v == 32) hipLaunchKernelGGL(gemm_abl_kernel<2>, dim3(nt), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL(gemm_abl_kernel<3>, dim3(nt), dim3(512), 0, s, a);
-    return hipGetLastError();
-  }
-  if (big && (v == 34 || v == 35) && a.K / BK >= LEAD && (a.K / BK) % 2 == 0) {  // full-line fetch probes
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    if (v == 34) hipLaunchKernelGGL(gemm_abl_kernel<4>, dim3(nt), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL(gemm_abl_kernel<5>, dim3(nt), dim3(512), 0, s, a);
-    return hipGetLastError();
-  }
-  if (big && v == 8 && a.K / BK >= LEAD) {
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    hipLaunchKernelGGL((gemm_pp_kernel<EPI_NONE, 1, false>), dim3(nt), dim3(512), 0, s, a);
-    return hipGetLastError();
-  }
-  if (v == 16) v = 3;
-  GemmArgs ga = a;
-  if (v == 6) {  // ping-pong with the grouped (L2-resident W panel) tile order
-    v = 3;
-    ga.ngroup = n_group(a.N / 256, a.K);
-  }
-  if (big && v >= 2 && v <= 5 && a.K / BK >= LEAD) {
-    const GemmArgs& a = ga;
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    if (v == 2) hipLaunchKernelGGL((gemm_pp_kernel<EPI, 2, false>), dim3(nt), dim3(512), 0, s, a);
-    else if (v == 3) hipLaunchKernelGGL((gemm_pp_kernel<EPI, 1, false>), dim3(nt), dim3(512), 0, s, a);
-    else if (v == 4) hipLaunchKernelGGL((gemm_pp_kernel<EPI, 2, true>), dim3(nt), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((gemm_pp_kernel<EPI, 1, true>), dim3(nt), dim3(512), 0, s, a);
-  } else if (big) {
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    const int g = nt < cu_count() ? nt : cu_count();
-    hipLaunchKernelGGL((gemm_kernel<EPI, 256, 256, 2, 4>), dim3(g), dim3(512), 0, s, a);
-  } else {
-    const int nt = ((a.M + 127) / 128) * (a.N / 128);
-    const int g = nt < 2 * cu_count() ? nt : 2 * cu_count();
-    hipLaunchKernelGGL((gemm_kernel<EPI, 128, 128, 2, 2>), dim3(g), dim3(256), 0, s, a);
-  }
-  return hipGetLastError();
 }
 
 #endif  // MICLIP_AB
@@ -1108,11 +1028,12 @@ template <int EPI>
 hipError_t launch(const GemmArgs& a, hipStream_t s) {
   const bool big = a.N % 256 == 0 && a.M >= 1024;
   const bool bf16_out = EPI == EPI_BF16 || EPI == EPI_GELU_BF16;
+  const bool staged = big && a.K / BK >= LEAD;
+  const int cus = cu_count();
+  const int nt = tile_count(a, 256, 256);
   if (a.patch_R) {  // fused patch gather: f32 output rows, ping-pong only
     if (!big || a.K != 3 * 32 * 32 || (a.patch_R & 31)) return hipErrorInvalidValue;
-    const int nt = ((a.M + 255) / 256) * (a.N / 256);
-    hipLaunchKernelGGL((gemm_pp_kernel<EPI, 1, false, false, false, true>), dim3(nt), dim3(512), 0, s, a);
-    return hipGetLastError();
+    return launch_kernel(gemm_pp_kernel<EPI, 1, false, false, false, true>, nt, 512, s, a);
   }
   if (a.a_f16) {   // split-f16 operands (fp32 tower): f32 epilogues with the rsc / csc factors
     if ((EPI != EPI_F32 && EPI != EPI_RESID_F32 && EPI != EPI_SPLIT_GELU) || !a.rsc || !a.csc || a.variant)
@@ -1120,33 +1041,18 @@ hipError_t launch(const GemmArgs& a, hipStream_t s) {
     if (EPI == EPI_SPLIT_GELU && (!a.rmax || !a.rsc_out || a.group || a.ldo != (a.o_dup ? 2 : 3) * (int64_t)a.N))
       return hipErrorInvalidValue;
     if constexpr (EPI == EPI_F32 || EPI == EPI_RESID_F32 || EPI == EPI_SPLIT_GELU) {
-      // the 8-phase kernel (gemm_8q.hip) wherever it applies; MICLIP_F32_8Q=0 (A/B build) keeps the
-      // ping-pong kernel below
-#if MICLIP_AB
-      // (MICLIP_F32_8Q=1 + MICLIP_F32_8Q_MASK: 1 EPI_F32, 2 EPI_RESID_F32, 4 EPI_SPLIT_GELU on the 8-phase kernel)
-      const char* e8 = std::getenv("MICLIP_F32_8Q");
-      const char* em = std::getenv("MICLIP_F32_8Q_MASK");
+      // the 8-phase kernel (gemm_8q.hip) wherever it applies; A/B build: MICLIP_F32_8Q=0 keeps the
+      // ping-pong kernel below, MICLIP_F32_8Q_MASK picks the epilogues that take the 8-phase kernel
+      // (1 EPI_F32, 2 EPI_RESID_F32, 4 EPI_SPLIT_GELU)
       const int bit = EPI == EPI_F32 ? 1 : (EPI == EPI_RESID_F32 ? 2 : 4);
-      const bool use8q = (!e8 || std::atoi(e8) != 0) && (!em || (std::atoi(em) & bit));
-#else
-      const bool use8q = true;
-#endif
+      const bool use8q = ab_env_int("MICLIP_F32_8Q", 1) != 0 && (ab_env_int("MICLIP_F32_8Q_MASK", 7) & bit);
       // (the 8-phase kernel's f32 epilogues assume a bias: bias-less calls take the ping-pong kernel)
-      if (use8q && a.bias && gemm_8q_ok(a)) return gemm_8q(a, EPI, s, cu_count(), 0);
+      if (use8q && a.bias && gemm_8q_ok(a)) return gemm_8q(a, EPI, s, cus, 0);
       if (a.a_dup || a.o_dup) return hipErrorInvalidValue;   // the [x1 | x2] layouts: the 8-phase kernel only
-      const int ntf = ((a.M + 255) / 256) * (a.N / 256);
-      if (big && a.K / BK >= LEAD) {
-        hipLaunchKernelGGL((gemm_pp_kernel<EPI, 1, false, false, false, false, true>), dim3(ntf), dim3(512), 0, s, a);
-      } else if (big) {
-        const int g = ntf < cu_count() ? ntf : cu_count();
-        hipLaunchKernelGGL((gemm_kernel<EPI, 256, 256, 2, 4, true>), dim3(g), dim3(512), 0, s, a);
-      } else {
-        const int nt2 = ((a.M + 127) / 128) * (a.N / 128);
-        const int g = nt2 < 2 * cu_count() ? nt2 : 2 * cu_count();
-        hipLaunchKernelGGL((gemm_kernel<EPI, 128, 128, 2, 2, true>), dim3(g), dim3(256), 0, s, a);
-      }
+      if (staged) return launch_kernel(gemm_pp_kernel<EPI, 1, false, false, false, false, true>, nt, 512, s, a);
+      return launch_tiled<EPI, true>(a, big, s);
     }
-    return hipGetLastError();
+    return hipErrorInvalidValue;   // (not reached: the epilogue check above)
   }
 #if MICLIP_AB
   if (a.variant != 0) return launch_ab<EPI>(a, s);
@@ -1158,49 +1064,24 @@ hipError_t launch(const GemmArgs& a, hipStream_t s) {
   // CUs, the same k order and epilogue arithmetic (bit-identical for EPI_BF16).  B/32 encode_text
   // of 32 queries 1272 -> 1134 us (scripts/text_micro.py, profiles/r05_zl_text_micro.log).
   // MICLIP_SMALLM=t (A/B build) moves the threshold (0: off).
-  int small_t = 64;
-#if MICLIP_AB
-  if (const char* sm = std::getenv("MICLIP_SMALLM")) small_t = std::atoi(sm);
-#endif
+  const int small_t = ab_env_int("MICLIP_SMALLM", 64);
   // Fewer 128 x 128 tiles than CUs (the text tower's in_proj / out_proj / c_proj at 32 queries):
   // 64 x 64 tiles, bit-identical again (round 6: encode_text of 32 queries 1131 -> 1006 us,
   // scripts/text_micro.py, profiles/r06_v_text_micro.log).  A/B MICLIP_SMALL64=u moves the
   // threshold to u tiles of 128 x 128 (0: off).
-  int small64 = cu_count();
-#if MICLIP_AB
-  if (const char* sm = std::getenv("MICLIP_SMALL64")) small64 = std::atoi(sm);
-#endif
-  if (EPI == EPI_BF16 && ((a.M + 255) / 256) * (a.N / 256) < small_t && a.N % 128 == 0 && !a.group) {
-    const int nt2 = ((a.M + 127) / 128) * (a.N / 128);
-    if (nt2 < small64) {
-      const int nt3 = ((a.M + 63) / 64) * (a.N / 64);
-      const int g = nt3 < 4 * cu_count() ? nt3 : 4 * cu_count();
-      hipLaunchKernelGGL((gemm_kernel<EPI, 64, 64, 2, 2>), dim3(g), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
-    const int g = nt2 < 2 * cu_count() ? nt2 : 2 * cu_count();
-    hipLaunchKernelGGL((gemm_kernel<EPI, 128, 128, 2, 2>), dim3(g), dim3(256), 0, s, a);
-    return hipGetLastError();
+  const int small64 = ab_env_int("MICLIP_SMALL64", cus);
+  if (EPI == EPI_BF16 && nt < small_t && a.N % 128 == 0 && !a.group) {
+    const int nt2 = tile_count(a, 128, 128);
+    if (nt2 < small64)
+      return launch_kernel(gemm_kernel<EPI, 64, 64, 2, 2>, persistent_grid(tile_count(a, 64, 64), 4 * cus), 256, s, a);
+    return launch_kernel(gemm_kernel<EPI, 128, 128, 2, 2>, persistent_grid(nt2, 2 * cus), 256, s, a);
   }
-  if (bf16_out && gemm_8q_ok(a)) return gemm_8q(a, EPI, s, cu_count(), 0);
-  const int nt = ((a.M + 255) / 256) * (a.N / 256);
-  const bool staged = big && a.K / BK >= LEAD;
-  if (staged && bf16_out && !a.group && (a.N >= 2048 || a.K <= 1024)) {   // persistent ping-pong (18)
-    const int grid = nt < cu_count() ? nt : cu_count();
-    hipLaunchKernelGGL((gemm_ppp_kernel<EPI>), dim3(grid), dim3(512), 0, s, a);
-  } else if (staged && bf16_out) {                                         // ping-pong, direct row stores (16)
-    hipLaunchKernelGGL((gemm_pp_kernel<EPI, 1, false, true>), dim3(nt), dim3(512), 0, s, a);
-  } else if (staged) {                                                     // ping-pong, LDS-staged f32 rows (3)
-    hipLaunchKernelGGL((gemm_pp_kernel<EPI, 1, false>), dim3(nt), dim3(512), 0, s, a);
-  } else if (big) {
-    const int g = nt < cu_count() ? nt : cu_count();
-    hipLaunchKernelGGL((gemm_kernel<EPI, 256, 256, 2, 4>), dim3(g), dim3(512), 0, s, a);
-  } else {
-    const int nt2 = ((a.M + 127) / 128) * (a.N / 128);
-    const int g = nt2 < 2 * cu_count() ? nt2 : 2 * cu_count();
-    hipLaunchKernelGGL((gemm_kernel<EPI, 128, 128, 2, 2>), dim3(g), dim3(256), 0, s, a);
-  }
-  return hipGetLastError();
+  if (bf16_out && gemm_8q_ok(a)) return gemm_8q(a, EPI, s, cus, 0);
+  if (staged && bf16_out && !a.group && (a.N >= 2048 || a.K <= 1024))   // persistent ping-pong (18)
+    return launch_kernel(gemm_ppp_kernel<EPI>, persistent_grid(nt, cus), 512, s, a);
+  if (staged && bf16_out) return launch_kernel(gemm_pp_kernel<EPI, 1, false, true>, nt, 512, s, a);   // direct row stores (16)
+  if (staged) return launch_kernel(gemm_pp_kernel<EPI, 1, false>, nt, 512, s, a);   // LDS-staged f32 rows (3)
+  return launch_tiled<EPI>(a, big, s);
 }
 
 }  // namespace

@@ -20,8 +20,7 @@
 //   [k-step 0 fragments of stage g + 1 read]  [k-step 1 MFMAs + columns 32-63, the block's stores]
 // LDS images, DMA permutation, k order of the MFMA chain (C = 0 at a tile's first k-step)
 // and the epilogue's arithmetic are gemm_8q's, so the output is bit-identical to it.
-#include "common.hpp"
-#include "internal.hpp"
+#include "gemm_common.hpp"
 
 namespace miclip {
 namespace {
@@ -35,58 +34,7 @@ constexpr int D_STAGE = D_ABYTES + D_BN * D_BK * 2;   // 48 KB
 constexpr int D_VEC = 2 * D_BN * 4 * 2 + 2 * D_BM * 8;   // bias, colv [2][BN]; rs [2][BM][2]
 constexpr int D_LDS = D_NS * D_STAGE + D_VEC;
 
-typedef _Float16 f16x8_d __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4_d __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void tile_coords_d(int t, int tiles_m, int tiles_n, int ng, int& mb, int& nb) {
-  if (ng <= 0 || ng >= tiles_n) {
-    mb = t / tiles_n;
-    nb = t % tiles_n;
-    return;
-  }
-  const int per = tiles_m * ng;
-  const int gg = t / per, r = t - gg * per;
-  const int ngg = min(ng, tiles_n - gg * ng);
-  mb = r / ngg;
-  nb = gg * ng + r % ngg;
-}
-
-// QuickGELU in stage order over 4 pairs, "+ 1" as packed adds (gemm_8q quick_gelu_stage_8q's
-// arithmetic per value: bit-identical whatever the group size)
-__device__ __forceinline__ void quick_gelu8_d(f32x2 (&v)[4]) {
-  float e[8];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f32x2 t = v[k] * (f32x2){-2.45546696f, -2.45546696f};
-    e[2 * k] = t.x;
-    e[2 * k + 1] = t.y;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) e[k] = __builtin_amdgcn_exp2f(e[k]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f32x2 p = (f32x2){e[2 * k], e[2 * k + 1]} + (f32x2){1.0f, 1.0f};
-    e[2 * k] = p.x;
-    e[2 * k + 1] = p.y;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) e[k] = __builtin_amdgcn_rcpf(e[k]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = v[k] * (f32x2){e[2 * k], e[2 * k + 1]};
-}
-
-// lane id through asm: opaque to CSE / LICM, so offsets derived from it are rebuilt where used
-// instead of hoisted out of the tile loop and held (or spilled) for the kernel's life
-__device__ __forceinline__ int lane_d() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-
-template <int N>
-__device__ __forceinline__ void vmwait_d() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int ABL, int NST>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_1d_kernel(GemmArgs a) {
@@ -107,7 +55,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   auto coords = [&](int v, int& mm, int& nn) __attribute__((always_inline)) {
     const int t = xcd_remap(v, ntiles);
     int mb, nb;
-    tile_coords_d(t, tiles_m, tiles_n, a.ngroup, mb, nb);
+    tile_coords(t, tiles_m, tiles_n, a.ngroup, mb, nb);
     mm = mb * D_BM;
     nn = nb * D_BN;
   };
@@ -129,7 +77,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int kofs = ls * D_BK * 2;
     // per-lane source offsets from the opaque lane id (row 8 i + (l >> 3) of the operand, 16-byte
     // chunk (l & 7) ^ ((row >> 1) & 7)): VALU per DMA instead of 12 hoisted row offsets in SGPRs
-    const int l = lane_d(), drow = l >> 3;
+    const int l = lane_id(), drow = l >> 3;
     const int ce = (l & 7) ^ (l >> 4), co = (l & 7) ^ (4 + (l >> 4));
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -160,20 +108,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const float* src = (wave == 0 ? a.bias : a.colv) + n0;
         float* dst = (wave == 0 ? sbias : scol) + par * D_BN;
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)src, (short)0, 512, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (LDS_AS void*)dst, 16, (uint32_t)lane_d() * 16, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (LDS_AS void*)dst, 16, (uint32_t)lane_id() * 16, 0, 0, 0);
       }
     } else {
       const __amdgpu_buffer_rsrc_t r =
           __builtin_amdgcn_make_buffer_rsrc((void*)(a.rs + (int64_t)(m0 + (wave - 2) * 128) * 2), (short)0, 1024, 0x00020000);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (LDS_AS void*)(srs + par * D_BM * 2 + (wave - 2) * 256), 16,
-                                               (uint32_t)lane_d() * 16, 0, 0, 0);
+                                               (uint32_t)lane_id() * 16, 0, 0, 0);
     }
   };
 
   // ---- fragments: lane (fr, fq) reads row fr of a 16-row block, k 8 fq .. + 7 (k-step 0) or
   // 32 + 8 fq .. (k-step 1), slot permuted by (fr >> 1)
   auto rdof = [&](int ks) __attribute__((always_inline)) {
-    const int l = lane_d(), lfr = l & 15, lfq = l >> 4;
+    const int l = lane_id(), lfr = l & 15, lfq = l >> 4;
     return lfr * 128 + (((4 * ks + lfq) ^ (lfr >> 1)) << 4);
   };
   bf16x8 fa0[8], fb0[4], fa1[8], fb1[4];
@@ -215,7 +163,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni)
         acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-            __builtin_bit_cast(f16x8_d, fb[ni]), __builtin_bit_cast(f16x8_d, fa[mi]),
+            __builtin_bit_cast(f16x8, fb[ni]), __builtin_bit_cast(f16x8, fa[mi]),
             first ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[mi][ni], 0, 0, 0);
   };
 
@@ -229,7 +177,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   u32x4_d dp0;   // the block's p = 0 piece, from half 0 to half 1
   // the half's LN vectors (asm LDS reads, issued before the 12 fragment reads: lgkmcnt(12) waits)
   auto epi_vectors = [&](int mi, int h) __attribute__((always_inline)) {
-    const int l = lane_d(), fr = l & 15, fq = l >> 4;
+    const int l = lane_id(), fr = l & 15, fq = l >> 4;
     const uint32_t ba = (uint32_t)(uintptr_t)(const LDS_AS float*)(sbias + pp * D_BN + wn * 64 + 32 * h + 4 * fq);
     const uint32_t ca = (uint32_t)(uintptr_t)(const LDS_AS float*)(scol + pp * D_BN + wn * 64 + 32 * h + 4 * fq);
     const uint32_t ra = (uint32_t)(uintptr_t)(const LDS_AS float*)(srs + pp * D_BM * 2 + (wm * 128 + mi * 16 + fr) * 2);
@@ -257,7 +205,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       gw[2 * q] = lo;
       gw[2 * q + 1] = hi;
     }
-    quick_gelu8_d(gw);
+    quick_gelu_stage<4, true>(gw);
     const uint32_t x0 = pack_bf16x2(gw[0]), y0 = pack_bf16x2(gw[1]);
     const uint32_t x1 = pack_bf16x2(gw[2]), y1 = pack_bf16x2(gw[3]);
     const auto sx = __builtin_amdgcn_permlane16_swap(x0, x1, false, false);
@@ -277,7 +225,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const u32x4_d dp1 = epi_half(acc, mi, 1);
     // whole 128-B rows: lane fr < 8 keeps its p = 0 piece of row fr and takes row fr + 8's p = 0
     // piece for store 2; lane fr >= 8 takes row fr - 8's p = 1 piece for store 1 (gemm_8q F_FULL)
-    const int l = lane_d(), fr = l & 15, fq = l >> 4;
+    const int l = lane_id(), fr = l & 15, fq = l >> 4;
     const bool top = fr < 8;
     u32x4_d s1, s2;
 #pragma unroll
@@ -306,7 +254,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   issue(0);
   issue(1);
   issue(2);
-  vmwait_d<24>();
+  vm_wait<24>();
   barrier();
   read_frags(0, rdof(0), fa0, fb0);
 
@@ -344,18 +292,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // vectors (issued after the DMAs of a tile's stage 0), the epilogue stores of stages g - 2 and
     // g - 1 (2 each, after their middles), stage g + 2's 12 DMAs
     if (!HP) {
-      if (S == 1 || S == 2) vmwait_d<13>();
-      else vmwait_d<12>();
+      if (S == 1 || S == 2) vm_wait<13>();
+      else vm_wait<12>();
     } else if (S == 0 || S >= 10) {
-      vmwait_d<12>();
+      vm_wait<12>();
     } else if (S == 1) {
-      vmwait_d<15>();
+      vm_wait<15>();
     } else if (S == 2) {
-      vmwait_d<17>();
+      vm_wait<17>();
     } else if (S == 9) {
-      vmwait_d<14>();
+      vm_wait<14>();
     } else {   // 3 .. 8
-      vmwait_d<16>();
+      vm_wait<16>();
     }
     barrier();
     issue(buf);   // stage g + 3 into the buffer just read
@@ -424,7 +372,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 #undef D_VWAIT
 #undef D_FWAIT
-  vmwait_d<0>();   // trailing DMAs land before the workgroup's LDS is released; stores retire
+  vm_wait<0>();   // trailing DMAs land before the workgroup's LDS is released; stores retire
 }
 
 }  // namespace
@@ -447,14 +395,12 @@ hipError_t gemm_1d(const GemmArgs& a0, int abl, hipStream_t s, int cus) {
         break;
       }
   }
-  const int nt = ((a.M + D_BM - 1) / D_BM) * (a.N / D_BN);
-  const int grid = nt < cus ? nt : cus;
+  const int grid = persistent_grid(tile_count(a, D_BM, D_BN), cus);
   const int nst = a.K / D_BK;
-  if (nst == 12 && abl == 4) hipLaunchKernelGGL((gemm_1d_kernel<4, 12>), dim3(grid), dim3(256), 0, s, a);
-  else if (nst == 12) hipLaunchKernelGGL((gemm_1d_kernel<0, 12>), dim3(grid), dim3(256), 0, s, a);
-  else if (nst == 16) hipLaunchKernelGGL((gemm_1d_kernel<0, 16>), dim3(grid), dim3(256), 0, s, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  auto go = [&](auto kernel) { return launch_kernel(kernel, grid, 256, s, a); };
+  if (nst == 12) return abl == 4 ? go(gemm_1d_kernel<4, 12>) : go(gemm_1d_kernel<0, 12>);
+  if (nst == 16) return go(gemm_1d_kernel<0, 16>);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace miclip

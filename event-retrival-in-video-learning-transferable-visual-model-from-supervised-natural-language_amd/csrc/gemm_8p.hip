@@ -51,54 +51,12 @@
 // s ^ ((r >> 1) & 7) (conflict-free ds_read_b128 lane groups); the DMA applies
 // the same permutation to its per-lane SOURCE address (lane-linear LDS side,
 // guide §5.4 rule 21).
-#include <type_traits>
-
-#include "common.hpp"
-#include "internal.hpp"
+#include "gemm_common.hpp"
 
 namespace miclip {
 namespace {
 
-constexpr int BM = 256, BN = 256, BK8 = 64;
-constexpr int HALF = 128 * BK8 * 2;   // 16 KB half-tile
-constexpr int BUF = 4 * HALF;         // 64 KB K-tile buffer
-// half-tile ids (issue/read order) and their slots in a buffer
-constexpr int H_A0 = 0, H_B0 = 1, H_B1 = 2, H_A1 = 3;
-
-// QuickGELU x * sigmoid(1.702 x) on a pair: packed FP32 multiplies/adds
-// (v_pk_*), one v_exp_f32 (2^x, the 1.702 * log2(e) scale folded) and one
-// v_rcp_f32 per value
-__device__ __forceinline__ f32x2 quick_gelu2_8p(f32x2 v) {
-  const f32x2 t = v * (f32x2){-2.45546696f, -2.45546696f};
-  f32x2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-  e = e + 1.0f;
-  return v * (f32x2){__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-}
-
-// bias read the compiler does not see (a plain LDS read would make hipcc
-// drain the in-flight DMAs with vmcnt(0), gemm.hip lds_read_f4)
-__device__ __forceinline__ float4 lds_read_f4_8p(const float* p) {
-  float4 v;
-  const uint32_t addr = (uint32_t)(uintptr_t)(const LDS_AS float*)p;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-
-__device__ __forceinline__ void tile_coords_8p(int t, int tiles_m, int tiles_n, int ng, int& mb, int& nb) {
-  if (ng <= 0 || ng >= tiles_n) {
-    mb = t / tiles_n;
-    nb = t % tiles_n;
-    return;
-  }
-  const int per = tiles_m * ng;
-  const int gg = t / per, r = t - gg * per;
-  const int ngg = min(ng, tiles_n - gg * ng);
-  mb = r / ngg;
-  nb = gg * ng + r % ngg;
-}
-
-template <int P>
-using PhaseC = std::integral_constant<int, P>;
+constexpr int BM = 256, BN = 256;   // (BK8, HALF, BUF and the half-tile ids: gemm_common.hpp)
 
 // ABL (timing probes, gemm.hip variants 91-96): 1 = no operand DMAs, 2 = no MFMAs, 3 = no output
 // stores, 4 = no epilogue (bias/activation/pack/stores), 6 = full-line store shape (wrong layout),
@@ -120,7 +78,7 @@ __global__ __launch_bounds__(512) void gemm_8p_kernel(GemmArgs a) {
   auto coords = [&](int v, int& mm, int& nn) {
     const int t = xcd_remap(v, ntiles);
     int mb, nb;
-    tile_coords_8p(t, tiles_m, tiles_n, a.ngroup, mb, nb);
+    tile_coords(t, tiles_m, tiles_n, a.ngroup, mb, nb);
     mm = mb * BM;
     nn = nb * BN;
   };
@@ -280,14 +238,14 @@ __global__ __launch_bounds__(512) void gemm_8p_kernel(GemmArgs a) {
     for (int pp = 0; pp < npairs; ++pp) {
       first_pair = pp == 0;
       const bool lastp = pp == npairs - 1;
-      phase(PhaseC<1>{}, lastp);
-      phase(PhaseC<2>{}, lastp);
-      phase(PhaseC<3>{}, lastp);
-      phase(PhaseC<4>{}, lastp);
-      phase(PhaseC<5>{}, lastp);
-      phase(PhaseC<6>{}, lastp);
-      phase(PhaseC<7>{}, lastp);
-      phase(PhaseC<8>{}, lastp);
+      phase(Phase<1>{}, lastp);
+      phase(Phase<2>{}, lastp);
+      phase(Phase<3>{}, lastp);
+      phase(Phase<4>{}, lastp);
+      phase(Phase<5>{}, lastp);
+      phase(Phase<6>{}, lastp);
+      phase(Phase<7>{}, lastp);
+      phase(Phase<8>{}, lastp);
     }
     if (ALN && wr == 0) barrier();   // ALN: both M-groups run the epilogue in the same interval
     if (EARLY) {
@@ -303,7 +261,7 @@ __global__ __launch_bounds__(512) void gemm_8p_kernel(GemmArgs a) {
     float4 bias[4];
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni)
-      bias[ni] = a.bias ? lds_read_f4_8p(sbias + cpar * BN + wc * 64 + ni * 16 + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+      bias[ni] = a.bias ? lds_read_f4(sbias + cpar * BN + wc * 64 + ni * 16 + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int mi = 0; mi < 8; ++mi) {
       const int m = cm0 + wr * 128 + mi * 16 + fr;
@@ -321,8 +279,8 @@ __global__ __launch_bounds__(512) void gemm_8p_kernel(GemmArgs a) {
           f32x2 lo = (f32x2){acc[mi][ni][0], acc[mi][ni][1]} + (f32x2){bias[ni].x, bias[ni].y};
           f32x2 hi = (f32x2){acc[mi][ni][2], acc[mi][ni][3]} + (f32x2){bias[ni].z, bias[ni].w};
           if (EPI == EPI_GELU_BF16) {
-            lo = quick_gelu2_8p(lo);
-            hi = quick_gelu2_8p(hi);
+            lo = quick_gelu_exp2(lo);
+            hi = quick_gelu_exp2(hi);
           }
           pk[qq] = make_uint2(pack_bf16x2(lo), pack_bf16x2(hi));
         }
@@ -356,49 +314,21 @@ int gemm_8p_ok(const GemmArgs& a) {
   return a.N % BN == 0 && a.K % (2 * BK8) == 0 && a.M >= BM && !a.group && !a.patch_R;
 }
 
-template <int EPI>
-static hipError_t launch_probe(const GemmArgs& a, hipStream_t s, int grid, int abl) {
-  if (abl == 1) hipLaunchKernelGGL((gemm_8p_kernel<EPI, 1>), dim3(grid), dim3(512), 0, s, a);
-  else if (abl == 2) hipLaunchKernelGGL((gemm_8p_kernel<EPI, 2>), dim3(grid), dim3(512), 0, s, a);
-  else if (abl == 3) hipLaunchKernelGGL((gemm_8p_kernel<EPI, 3>), dim3(grid), dim3(512), 0, s, a);
-  else if (abl == 4) hipLaunchKernelGGL((gemm_8p_kernel<EPI, 4>), dim3(grid), dim3(512), 0, s, a);
-  else if (abl == 6) hipLaunchKernelGGL((gemm_8p_kernel<EPI, 6>), dim3(grid), dim3(512), 0, s, a);
-  else if (abl == 7) hipLaunchKernelGGL((gemm_8p_kernel<EPI, 7>), dim3(grid), dim3(512), 0, s, a);
-  else if (abl == 8) hipLaunchKernelGGL((gemm_8p_kernel<EPI, 8>), dim3(grid), dim3(512), 0, s, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
+// abl: 0 = the schedule; 100 aligned epilogue, 101 early phase-1 DMAs, 102 both; 1-4, 6-8 = the ABL probes
 hipError_t gemm_8p(const GemmArgs& a, int epi, hipStream_t s, int cus, int abl) {
-  const int nt = ((a.M + BM - 1) / BM) * (a.N / BN);
-  const int grid = nt < cus ? nt : cus;
-  if (abl == 101) {   // early phase-1 DMAs
-    if (epi == EPI_GELU_BF16) hipLaunchKernelGGL((gemm_8p_kernel<EPI_GELU_BF16, 0, false, true>), dim3(grid), dim3(512), 0, s, a);
-    else if (epi == EPI_BF16) hipLaunchKernelGGL((gemm_8p_kernel<EPI_BF16, 0, false, true>), dim3(grid), dim3(512), 0, s, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-  }
-  if (abl == 102) {   // early phase-1 DMAs + aligned epilogue
-    if (epi == EPI_GELU_BF16) hipLaunchKernelGGL((gemm_8p_kernel<EPI_GELU_BF16, 0, true, true>), dim3(grid), dim3(512), 0, s, a);
-    else if (epi == EPI_BF16) hipLaunchKernelGGL((gemm_8p_kernel<EPI_BF16, 0, true, true>), dim3(grid), dim3(512), 0, s, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-  }
-  if (abl == 100) {   // aligned epilogue
-    if (epi == EPI_GELU_BF16) hipLaunchKernelGGL((gemm_8p_kernel<EPI_GELU_BF16, 0, true>), dim3(grid), dim3(512), 0, s, a);
-    else if (epi == EPI_BF16) hipLaunchKernelGGL((gemm_8p_kernel<EPI_BF16, 0, true>), dim3(grid), dim3(512), 0, s, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-  }
-  if (abl) {
-    if (epi == EPI_GELU_BF16) return launch_probe<EPI_GELU_BF16>(a, s, grid, abl);
-    if (epi == EPI_BF16) return launch_probe<EPI_BF16>(a, s, grid, abl);
-    return hipErrorInvalidValue;
-  }
-  if (epi == EPI_GELU_BF16) hipLaunchKernelGGL(gemm_8p_kernel<EPI_GELU_BF16>, dim3(grid), dim3(512), 0, s, a);
-  else if (epi == EPI_BF16) hipLaunchKernelGGL(gemm_8p_kernel<EPI_BF16>, dim3(grid), dim3(512), 0, s, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  const int grid = persistent_grid(tile_count(a, BM, BN), cus);
+  return with_epi<EPI_GELU_BF16, EPI_BF16>(epi, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    auto go = [&](auto kernel) { return launch_kernel(kernel, grid, 512, s, a); };
+    switch (abl) {
+      case 0: return go(gemm_8p_kernel<E>);
+      case 100: return go(gemm_8p_kernel<E, 0, true>);
+      case 101: return go(gemm_8p_kernel<E, 0, false, true>);
+      case 102: return go(gemm_8p_kernel<E, 0, true, true>);
+      default:
+        return with_value<1, 2, 3, 4, 6, 7, 8>(abl, [&](auto p) { return go(gemm_8p_kernel<E, decltype(p)::value>); });
+    }
+  });
 }
 
 }  // namespace miclip

@@ -55,24 +55,20 @@
 //    not a chip-wide write burst; scripts/gemm_probe8q.py stamps).
 // Result (scripts/gemm_micro.py, M = 500k, interleaved with v98 in one process):
 // fc -4..-7 %, qkv -3..-4 %, proj -6 %, out +-3 %; bit-identical to gemm_8p.
-#include <cstdlib>
 #include <cstring>
+#include <utility>
 
-#include "common.hpp"
-#include "internal.hpp"
+#include "gemm_common.hpp"
 
 namespace miclip {
 namespace {
 
-constexpr int BM = 256, BN = 256, BK8 = 64;
-constexpr int HALF = 128 * BK8 * 2;   // 16 KB half-tile
-constexpr int BUF = 4 * HALF;         // 64 KB K-tile buffer
-constexpr int H_A0 = 0, H_B0 = 1, H_B1 = 2, H_A1 = 3;
+constexpr int BM = 256, BN = 256;   // (BK8, HALF, BUF and the half-tile ids: gemm_common.hpp)
 // flags
 constexpr int F_GLDS = 1;   // flat global_load_lds with per-DMA address math (gemm_8p's) instead of descriptors
 constexpr int F_FULL = 2;   // epilogue stores of 8 whole 128-B rows (lane pairs fr, fr ^ 8 swap halves by DPP)
 constexpr int F_VOREC = 4;  // epilogue store offsets recomputed from the lane id (EPI_RES16 always)
-constexpr int F_GSTAGE = 8; // QuickGELU over a store's 8 values in stage order (quick_gelu8_8q)
+constexpr int F_GSTAGE = 8; // QuickGELU over a store's 8 values in stage order (quick_gelu_stage<4>)
 constexpr int F_GSTAGE16 = 32;   // the same over a 16-row block's 16 values (A/B)
 constexpr int F_ANT = 64;   // A-operand DMAs non-temporal (A/B: keep the weight panel in L2 against the A stream)
 constexpr int F_ONT = 128;  // output stores non-temporal (A/B)
@@ -102,83 +98,11 @@ constexpr int F_DYN = 2048;
 constexpr int F_WARM = 4096;
 __device__ unsigned g_dyn8q[8];   // F_DYN: per-XCD claim counters, zeroed before each launch
 
-__device__ __forceinline__ f32x2 quick_gelu2_8q(f32x2 v) {
-  const f32x2 t = v * (f32x2){-2.45546696f, -2.45546696f};   // -1.702 * log2(e)
-  f32x2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-  e = e + 1.0f;
-  return v * (f32x2){__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-}
-
-// QuickGELU of 8 values in stage order (all multiplies, all exponentials, all adds, all
-// reciprocals, all products), so consecutive transcendental ops are independent (F_GSTAGE)
-// (PK: the adds as packed pairs -- the same additions, bit-identical; one wave alone issues a
-// v_pk_add_f32 in 5.1 cycles against 4.7 for a v_add_f32, scripts/probes/valu_rate.hip)
-template <int NP, bool PK = false>
-__device__ __forceinline__ void quick_gelu_stage_8q(f32x2 (&v)[NP]) {
-  float e[2 * NP];
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    const f32x2 t = v[k] * (f32x2){-2.45546696f, -2.45546696f};
-    e[2 * k] = t.x;
-    e[2 * k + 1] = t.y;
-  }
-#pragma unroll
-  for (int k = 0; k < 2 * NP; ++k) e[k] = __builtin_amdgcn_exp2f(e[k]);
-  if (PK) {
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const f32x2 p = (f32x2){e[2 * k], e[2 * k + 1]} + (f32x2){1.0f, 1.0f};
-      e[2 * k] = p.x;
-      e[2 * k + 1] = p.y;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 2 * NP; ++k) e[k] = e[k] + 1.0f;
-  }
-#pragma unroll
-  for (int k = 0; k < 2 * NP; ++k) e[k] = __builtin_amdgcn_rcpf(e[k]);
-#pragma unroll
-  for (int k = 0; k < NP; ++k) v[k] = v[k] * (f32x2){e[2 * k], e[2 * k + 1]};
-}
-__device__ __forceinline__ void quick_gelu8_8q(f32x2 (&v)[4]) { quick_gelu_stage_8q<4>(v); }
-
-// EPI_SPLIT_GELU's row exponent (gemm.hip split_exp_g): 2^e scales the row bound into [2^13, 2^14)
-__device__ __forceinline__ int split_exp_8q(float mx) {
-  if (!(mx > 0.f) || !__builtin_isfinite(mx)) return 0;
-  int ex;
-  (void)frexpf(mx, &ex);
-  const int e = 14 - ex;
-  return e > 126 ? 126 : (e < -126 ? -126 : e);
-}
-
-__device__ __forceinline__ void tile_coords_8q(int t, int tiles_m, int tiles_n, int ng, int& mb, int& nb) {
-  if (ng <= 0 || ng >= tiles_n) {
-    mb = t / tiles_n;
-    nb = t % tiles_n;
-    return;
-  }
-  const int per = tiles_m * ng;
-  const int gg = t / per, r = t - gg * per;
-  const int ngg = min(ng, tiles_n - gg * ng);
-  mb = r / ngg;
-  nb = gg * ng + r % ngg;
-}
-
 // timing probe (ABL 9, scripts/gemm_probe.py 8q): per workgroup and M-group, s_memtime stamps
 // of its third tile (see the S* comments) + two s_memrealtime stamps for the clock
 __device__ unsigned long long g_probe8q[1024 * 2 * 9];
 
-template <int P>
-struct Ph8q {
-  static constexpr int value = P;
-};
-template <bool V>
-struct BoolC {
-  static constexpr bool value = V;
-};
-
 // ABL (timing probes): 2 = no MFMAs, 4 = no epilogue work (accumulators kept live), 9 = stamps
-typedef _Float16 f16x8_8q __attribute__((ext_vector_type(8)));
 
 template <int EPI>
 struct EpiKind8q {
@@ -247,7 +171,7 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
   auto coords = [&](int v, int& mm, int& nn) {
     const int t = xcd_remap(v, ntiles);
     int mb, nb;
-    tile_coords_8q(t, tiles_m, tiles_n, a.ngroup, mb, nb);
+    tile_coords(t, tiles_m, tiles_n, a.ngroup, mb, nb);
     mm = mb * BM;
     nn = nb * BN;
   };
@@ -260,7 +184,7 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
   const int dxe = dxs + dq + (dxcd < dr ? 1 : 0);
   auto coords_l = [&](int t, int& mm, int& nn) {
     int mb, nb;
-    tile_coords_8q(t, tiles_m, tiles_n, a.ngroup, mb, nb);
+    tile_coords(t, tiles_m, tiles_n, a.ngroup, mb, nb);
     mm = mb * BM;
     nn = nb * BN;
   };
@@ -463,14 +387,9 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
   // cost ~30-50 us (probe ABL 11).
   typedef _Float16 h2_8q __attribute__((ext_vector_type(2)));
   u32x4_8q xin[8][2];
-  // lane id from an opaque asm, so offsets derived from it are computed where used (the 16
+  // store offsets from lane_id()'s opaque asm, so they are computed where used (the 16
   // store offsets voO + mi * blkO, derived from a kernel-scope constant, are otherwise hoisted
   // out of the tile loop and held in 16 VGPRs for the kernel's life)
-  auto lane_id = [&]() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-  };
   auto vo_out = [&](int l) {
     return (uint32_t)(((wr * 128 + (l & 15)) * a.ldo + wc * 64 + ((l >> 4) & 1) * 16 + (l >> 5) * 8) * 2);
   };
@@ -518,7 +437,7 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
 #define MI_VM_ISSUED(n) ((void)0)
 #endif
   auto epilogue_spl = [&]() __attribute__((always_inline)) {
-    int l;
+    int l;   // (lane_id()'s asm written out: through the helper hipcc schedules the EPI_SPLIT_GELU epilogue differently)
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     const int lr = l & 15, lg = l >> 4;
     float4 bias[4], cs[4];
@@ -595,7 +514,7 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
 #pragma unroll
       for (int mi = 0; mi < 8; ++mi) {
         const float bound = (rmv[mi] * a.bnd_w + a.bnd_b) * (1.0f + 0.00390625f);
-        const int e = split_exp_8q(bound);
+        const int e = split_exp(bound);
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
           uint2 k1[2], k2[2];
@@ -605,11 +524,8 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
             uint32_t h1[4], h2[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-              const float y = v[i] * (1.0f / (1.0f + expf(-1.702f * v[i])));
-              const float ys = ldexpf(y, e);
-              const _Float16 p1 = (_Float16)ys;
-              const float f1 = (float)p1;
-              const _Float16 p2 = __builtin_isfinite(f1) ? (_Float16)(ys - f1) : (_Float16)0.f;
+              _Float16 p1, p2;
+              split2h(ldexpf(quick_gelu_f32(v[i]), e), p1, p2);
               h1[i] = __builtin_bit_cast(uint16_t, p1);
               h2[i] = __builtin_bit_cast(uint16_t, p2);
             }
@@ -648,7 +564,7 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
       return;
     }
     float4 bias[4];
-    if (a.bias) {   // four reads under one wait, invisible to the compiler (gemm.hip lds_read_f4)
+    if (a.bias) {   // four reads under one wait, invisible to the compiler (gemm_common.hpp lds_read_f4)
       const uint32_t ba = (uint32_t)(uintptr_t)(const LDS_AS float*)(sbias + ppar * BN + wc * 64 + 4 * g);
       asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %4 offset:128\n\t"
                    "ds_read_b128 %3, %4 offset:192\n\ts_waitcnt lgkmcnt(0)"
@@ -665,7 +581,7 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
     // tile loop, and its reload's vmcnt(0) would drain the DMAs in flight)
     constexpr bool VOREC = EK::RES || (F & F_VOREC);
     int ln_ = 0;
-    if (EK::LN || VOREC) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln_));
+    if (EK::LN || VOREC) ln_ = lane_id();
     uint32_t vo = voO;
     if constexpr (VOREC) vo = vo_out(ln_);
     // (asm LDS reads: a compiler-visible LDS read waits vmcnt(0) for the LDS-DMAs in flight)
@@ -715,7 +631,7 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
           gw[2 * ni] = lo;
           gw[2 * ni + 1] = hi;
         }
-        quick_gelu_stage_8q<8, (F & F_GPK) != 0>(gw);
+        quick_gelu_stage<8, (F & F_GPK) != 0>(gw);
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) pkb[ni >> 1][ni & 1] = make_uint2(pack_bf16x2(gw[2 * ni]), pack_bf16x2(gw[2 * ni + 1]));
       }
@@ -746,13 +662,13 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
             continue;
           }
           if (EK::GELU) {
-            lo = quick_gelu2_8q(lo);
-            hi = quick_gelu2_8q(hi);
+            lo = quick_gelu_exp2(lo);
+            hi = quick_gelu_exp2(hi);
           }
           pk[qq] = make_uint2(pack_bf16x2(lo), pack_bf16x2(hi));
         }
         if (EK::GELU && (F & F_GSTAGE) && !(F & F_GSTAGE16)) {
-          quick_gelu8_8q(gv);
+          quick_gelu_stage<4>(gv);
 #pragma unroll
           for (int qq = 0; qq < 2; ++qq) pk[qq] = make_uint2(pack_bf16x2(gv[2 * qq]), pack_bf16x2(gv[2 * qq + 1]));
         }
@@ -951,7 +867,7 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
             // takes C = 0 as an inline constant: no zeroing pass between tiles
             if (OPF16)   // fp16 operands (the LN-folded GEMMs: x16 rows and W' = f16(W * gamma))
               acc[mh * 4 + mi][nh * 2 + ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                  __builtin_bit_cast(f16x8_8q, fb[ni][ks]), __builtin_bit_cast(f16x8_8q, fa[mi][ks]),
+                  __builtin_bit_cast(f16x8, fb[ni][ks]), __builtin_bit_cast(f16x8, fa[mi][ks]),
                   (FIRST && P <= 4 && ks == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[mh * 4 + mi][nh * 2 + ni], 0, 0, 0);
             else
               acc[mh * 4 + mi][nh * 2 + ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -976,14 +892,14 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
     barrier();
   };
   auto pair = [&](auto firstc, auto lastc) {
-    phase(Ph8q<1>{}, firstc, lastc);
-    phase(Ph8q<2>{}, firstc, lastc);
-    phase(Ph8q<3>{}, firstc, lastc);
-    phase(Ph8q<4>{}, firstc, lastc);
-    phase(Ph8q<5>{}, firstc, lastc);
-    phase(Ph8q<6>{}, firstc, lastc);
-    phase(Ph8q<7>{}, firstc, lastc);
-    phase(Ph8q<8>{}, firstc, lastc);
+    phase(Phase<1>{}, firstc, lastc);
+    phase(Phase<2>{}, firstc, lastc);
+    phase(Phase<3>{}, firstc, lastc);
+    phase(Phase<4>{}, firstc, lastc);
+    phase(Phase<5>{}, firstc, lastc);
+    phase(Phase<6>{}, firstc, lastc);
+    phase(Phase<7>{}, firstc, lastc);
+    phase(Phase<8>{}, firstc, lastc);
   };
 
   if (a.stagger_phases > 1) {   // start stagger (see GemmArgs)
@@ -1031,9 +947,9 @@ __global__ __launch_bounds__(512) void gemm_8q_kernel(GemmArgs a) {
     cur_m0 = cm0;
     cur_n0 = cn0;
     // (npairs >= 2, gemm_8q_ok: a one-pair instance beside these made hipcc spill ~200 VGPRs)
-    pair(BoolC<true>{}, BoolC<false>{});
-    for (int pp = 1; pp < npairs - 1; ++pp) pair(BoolC<false>{}, BoolC<false>{});
-    pair(BoolC<false>{}, BoolC<true>{});
+    pair(std::bool_constant<true>{}, std::bool_constant<false>{});
+    for (int pp = 1; pp < npairs - 1; ++pp) pair(std::bool_constant<false>{}, std::bool_constant<false>{});
+    pair(std::bool_constant<false>{}, std::bool_constant<true>{});
     stamp(6);   // S6: tile end
     if ((ABL == 9 || ABL == 10) && ti == 2) st[8] = __builtin_amdgcn_s_memrealtime();
     ++ti;
@@ -1092,11 +1008,78 @@ int default_ngroup_8q(int tiles_n, int K) {
   return 0;
 }
 
+namespace {
+
+// The LayerNorm-folded kernels' epilogue flags (c_fc: EPI_LN_GELU_BF16, in_proj: EPI_LN_BF16).
+// c_fc: QuickGELU in stage order over each 16-row block's 16 values, its "+ 1" as packed adds,
+// store offsets from the lane id, and whole-line (128-B) non-temporal row stores -- all
+// bit-identical (lnfc500 2281 vs 2318 us for the 8-value order against none,
+// profiles/r04_ag_lnflags.log; the 16-value order 2296 vs 2354 us, profiles/r05_a_lnfc.log;
+// + packed adds + whole-line non-temporal stores 2239-2259 vs 2304-2311 us,
+// profiles/r05_d_lnfc.log).  in_proj: whole-line non-temporal stores, 1646 vs 1690 us
+// (r05_d_lnqkv.log; FETCH 5.4 -> 3.7x the operand bytes: the output no longer displaces the
+// weight panel from L2, profiles/r05_b_fullnt_gemm_traffic_ab.json).  Both: the lagging
+// M-group's epilogue beside the leading one's (F_BEARLY): c_fc 2143-2149 vs 2230 us, qkv 1606
+// vs 1615 us, bit-identical (profiles/r05_f_lnfc.log, r05_f_lnqkv.log)
+constexpr int F_G16 = F_GSTAGE16 | F_GSTAGE | F_VOREC;   // the 16-value stage order (it implies the other two)
+constexpr int F_LN = F_BEARLY | F_FULL | F_ONT;
+constexpr int F_LN_GELU = F_BEARLY | F_GPK | F_ONT | F_FULL | F_G16;
+
+#if MICLIP_AB
+// A/B (MICLIP_8Q_F = ff): the LayerNorm-folded kernels with other epilogue flags, one row per value
+// of the switch: the flags for EPI_LN_BF16 (no GELU: the stage orders have nothing to reorder, so
+// values that only choose one take F_VOREC alone) and for EPI_LN_GELU_BF16; -1: the value selects
+// nothing for that epilogue and the product flags run.  + 64: A DMAs non-temporal (F_ANT), + 128:
+// output stores non-temporal (F_ONT), + 2: whole-line (128-B) row stores (F_FULL); 1: no flag.
+// Both the admission of a value and the kernel it selects come from this table.
+struct F8qRow {
+  int ff, ln, ln_gelu;
+};
+constexpr int F_G8 = F_GSTAGE | F_VOREC;
+constexpr F8qRow F8Q_ROWS[] = {
+    {1, -1, 0},
+    {2, F_FULL, F_FULL | F_G16},
+    {4, F_VOREC, F_VOREC},
+    {8, F_VOREC, F_GSTAGE},
+    {12, F_VOREC, F_G8},
+    {44, F_VOREC, F_G16},
+    {46, F_FULL, F_FULL | F_G16},
+    {64, F_ANT, F_ANT | F_G8},
+    {76, F_ANT, F_ANT | F_G8},
+    {108, F_VOREC, F_ANT | F_G16},
+    {130, F_FULL | F_ONT, F_ONT | F_FULL | F_G16},
+    {140, F_VOREC, F_ONT | F_G8},
+    {174, F_FULL | F_ONT, F_ONT | F_FULL | F_G16},
+    {192, F_ANT | F_ONT, F_ONT | F_ANT | F_G8},
+    {204, F_ANT | F_ONT, F_ONT | F_ANT | F_G8},
+    {300, F_VOREC, F_GPK | F_G16},
+    {430, F_VOREC, F_GPK | F_ONT | F_FULL | F_G16},
+    {642, F_LN, F_LN_GELU},
+    {942, F_LN, F_LN_GELU},
+};
+// the row of ff, if it selects a kernel for EPI: launched into r (one instantiation per row's flags)
+template <int EPI, size_t... I>
+bool launch_8q_f(int ff, int grid, hipStream_t s, const GemmArgs& a, hipError_t& r, std::index_sequence<I...>) {
+  auto row = [&](auto i) {
+    constexpr F8qRow R = F8Q_ROWS[decltype(i)::value];
+    constexpr int FL = EPI == EPI_LN_BF16 ? R.ln : R.ln_gelu;
+    if constexpr (FL >= 0) {
+      if (ff == R.ff) {
+        r = launch_kernel(gemm_8q_kernel<EPI, 0, FL, true>, grid, 512, s, a);
+        return true;
+      }
+    }
+    return false;
+  };
+  return (row(std::integral_constant<size_t, I>{}) || ...);
+}
+#endif
+
+}  // namespace
+
 hipError_t gemm_8q(const GemmArgs& a0, int epi, hipStream_t s, int cus, int mode) {
   GemmArgs a = a0;
-#if MICLIP_AB   // A/B: MICLIP_8Q_NG forces the tile-order group width (-1 = m-major raster)
-  if (const char* ng = std::getenv("MICLIP_8Q_NG")) a.ngroup = std::atoi(ng);
-#endif
+  a.ngroup = ab_env_int("MICLIP_8Q_NG", a.ngroup);   // A/B: forces the tile-order group width (-1 = m-major raster)
   if (a.ngroup == 0) a.ngroup = default_ngroup_8q(a.N / BN, a.K);
   if (mode == 5 || mode == 6 || mode == 7 || mode == 8) {   // start-stagger probes: 2 / 4 / 2 phases of ~1/2, 1/4, 1/4 tile
     const int tile_ticks = (int)(2200LL * a.K / 768);   // ~22 us per 256 x 256 tile at K = 768
@@ -1104,85 +1087,32 @@ hipError_t gemm_8q(const GemmArgs& a0, int epi, hipStream_t s, int cus, int mode
     a.stagger_ticks = (mode == 5 || mode == 8) ? tile_ticks / 2 : tile_ticks / 4;
     mode = mode == 8 ? 9 : 0;   // 8: the stamp probe, staggered
   }
-  const int nt = ((a.M + BM - 1) / BM) * (a.N / BN);
-  const int grid = nt < cus ? nt : cus;
+  const int nt = tile_count(a, BM, BN);
+  const int grid = persistent_grid(nt, cus);
+  auto go = [&](auto kernel) { return launch_kernel(kernel, grid, 512, s, a); };
   // the LayerNorm-folded GEMMs read fp16 operands; their vectors must be present
   if (epi == EPI_LN_BF16 || epi == EPI_LN_GELU_BF16) {
     if (!a.a_f16 || !a.rs || !a.colv || !a.bias || mode) return hipErrorInvalidValue;
-#if MICLIP_AB   // A/B (MICLIP_8Q_F): epilogue flags F_VOREC (4) / F_GSTAGE (8) / both (12); 1 = none
-    const char* fe = std::getenv("MICLIP_8Q_F");
-    const int ff = fe ? std::atoi(fe) : 0;
-    // 1000: the deferred-epilogue one-wave kernel (gemm_1d.hip), 1004 its no-epilogue probe
-    if ((ff == 1000 || ff == 1004) && epi == EPI_LN_GELU_BF16) return gemm_1d(a0, ff - 1000, s, cus);
-    if (ff == 1 && epi == EPI_LN_GELU_BF16) {
-      hipLaunchKernelGGL((gemm_8q_kernel<EPI_LN_GELU_BF16, 0, 0, true>), dim3(grid), dim3(512), 0, s, a);
-      return hipGetLastError();
-    }
-    // + 64: A DMAs non-temporal (F_ANT), + 128: output stores non-temporal (F_ONT)
-    // + 2: whole-line (128-B) row stores (F_FULL), alone (46 / 2) or non-temporal (174 / 130)
-    if (ff == 4 || ff == 8 || ff == 12 || ff == 44 || ff == 64 || ff == 192 || ff == 76 || ff == 204 || ff == 108 ||
-        ff == 140 || ff == 46 || ff == 174 || ff == 2 || ff == 130 || ff == 300 || ff == 430 || ff == 942 ||
-        ff == 642) {
-#define LNF(E, FL) hipLaunchKernelGGL((gemm_8q_kernel<E, 0, FL, true>), dim3(grid), dim3(512), 0, s, a)
-      if (epi == EPI_LN_BF16) {
-        if (ff == 2 || ff == 46) LNF(EPI_LN_BF16, F_FULL);
-        else if (ff == 130 || ff == 174) LNF(EPI_LN_BF16, F_FULL | F_ONT);
-        else if (ff == 642 || ff == 942) LNF(EPI_LN_BF16, F_BEARLY | F_FULL | F_ONT);
-        else if (ff == 64 || ff == 76) LNF(EPI_LN_BF16, F_ANT);
-        else if (ff == 192 || ff == 204) LNF(EPI_LN_BF16, F_ANT | F_ONT);
-        else LNF(EPI_LN_BF16, F_VOREC);   // (no GELU: F_GSTAGE has nothing to reorder)
-      } else if (ff == 4) LNF(EPI_LN_GELU_BF16, F_VOREC);
-      else if (ff == 8) LNF(EPI_LN_GELU_BF16, F_GSTAGE);
-      else if (ff == 44) LNF(EPI_LN_GELU_BF16, F_GSTAGE16 | F_GSTAGE | F_VOREC);
-      else if (ff == 76 || ff == 64) LNF(EPI_LN_GELU_BF16, F_ANT | F_GSTAGE | F_VOREC);
-      else if (ff == 204 || ff == 192) LNF(EPI_LN_GELU_BF16, F_ONT | F_ANT | F_GSTAGE | F_VOREC);
-      else if (ff == 140) LNF(EPI_LN_GELU_BF16, F_ONT | F_GSTAGE | F_VOREC);
-      else if (ff == 108) LNF(EPI_LN_GELU_BF16, F_ANT | F_GSTAGE16 | F_GSTAGE | F_VOREC);
-      else if (ff == 46 || ff == 2) LNF(EPI_LN_GELU_BF16, F_FULL | F_GSTAGE16 | F_GSTAGE | F_VOREC);
-      else if (ff == 174 || ff == 130) LNF(EPI_LN_GELU_BF16, F_ONT | F_FULL | F_GSTAGE16 | F_GSTAGE | F_VOREC);
-      else if (ff == 300) LNF(EPI_LN_GELU_BF16, F_GPK | F_GSTAGE16 | F_GSTAGE | F_VOREC);
-      else if (ff == 430) LNF(EPI_LN_GELU_BF16, F_GPK | F_ONT | F_FULL | F_GSTAGE16 | F_GSTAGE | F_VOREC);
-      else if (ff == 942 || ff == 642)
-        LNF(EPI_LN_GELU_BF16, F_BEARLY | F_GPK | F_ONT | F_FULL | F_GSTAGE16 | F_GSTAGE | F_VOREC);
-      else LNF(EPI_LN_GELU_BF16, F_GSTAGE | F_VOREC);
-#undef LNF
-      return hipGetLastError();
-    }
-#endif
-    // c_fc: QuickGELU in stage order over each 16-row block's 16 values, its "+ 1" as packed adds,
-    // store offsets from the lane id, and whole-line (128-B) non-temporal row stores -- all
-    // bit-identical (lnfc500 2281 vs 2318 us for the 8-value order against none,
-    // profiles/r04_ag_lnflags.log; the 16-value order 2296 vs 2354 us, profiles/r05_a_lnfc.log;
-    // + packed adds + whole-line non-temporal stores 2239-2259 vs 2304-2311 us,
-    // profiles/r05_d_lnfc.log).  in_proj: whole-line non-temporal stores, 1646 vs 1690 us
-    // (r05_d_lnqkv.log; FETCH 5.4 -> 3.7x the operand bytes: the output no longer displaces the
-    // weight panel from L2, profiles/r05_b_fullnt_gemm_traffic_ab.json).  Both: the lagging
-    // M-group's epilogue beside the leading one's (F_BEARLY): c_fc 2143-2149 vs 2230 us, qkv 1606
-    // vs 1615 us, bit-identical (profiles/r05_f_lnfc.log, r05_f_lnqkv.log)
-#if MICLIP_AB   // A/B (MICLIP_8Q_DYN=1): the product flags + per-XCD claimed tile order (F_DYN)
-    if (const char* dy = std::getenv("MICLIP_8Q_DYN")) {
-      if (std::atoi(dy) == 1 && grid % 8 == 0 && nt >= grid) {
+    return with_epi<EPI_LN_BF16, EPI_LN_GELU_BF16>(epi, [&](auto e) {
+      constexpr int E = decltype(e)::value;
+      constexpr int FP = E == EPI_LN_BF16 ? F_LN : F_LN_GELU;   // the product flags
+#if MICLIP_AB
+      const int ff = ab_env_int("MICLIP_8Q_F", 0);
+      // 1000: the deferred-epilogue one-wave kernel (gemm_1d.hip), 1004 its no-epilogue probe
+      if ((ff == 1000 || ff == 1004) && E == EPI_LN_GELU_BF16) return gemm_1d(a0, ff - 1000, s, cus);
+      hipError_t r = hipSuccess;
+      if (launch_8q_f<E>(ff, grid, s, a, r, std::make_index_sequence<sizeof(F8Q_ROWS) / sizeof(F8Q_ROWS[0])>{})) return r;
+      // MICLIP_8Q_DYN=1: the product flags + per-XCD claimed tile order (F_DYN)
+      if (ab_env_int("MICLIP_8Q_DYN", 0) == 1 && grid % 8 == 0 && nt >= grid) {
         void* ctr = nullptr;
         if (hipGetSymbolAddress(&ctr, HIP_SYMBOL(g_dyn8q)) != hipSuccess) return hipErrorInvalidSymbol;
-        const hipError_t e = hipMemsetAsync(ctr, 0, sizeof(unsigned) * 8, s);
-        if (e != hipSuccess) return e;
-        if (epi == EPI_LN_BF16)
-          hipLaunchKernelGGL((gemm_8q_kernel<EPI_LN_BF16, 0, F_DYN | F_BEARLY | F_FULL | F_ONT, true>), dim3(grid), dim3(512), 0, s, a);
-        else
-          hipLaunchKernelGGL(
-              (gemm_8q_kernel<EPI_LN_GELU_BF16, 0, F_DYN | F_BEARLY | F_GPK | F_ONT | F_FULL | F_GSTAGE16 | F_GSTAGE | F_VOREC, true>),
-              dim3(grid), dim3(512), 0, s, a);
-        return hipGetLastError();
+        const hipError_t me = hipMemsetAsync(ctr, 0, sizeof(unsigned) * 8, s);
+        if (me != hipSuccess) return me;
+        return go(gemm_8q_kernel<E, 0, F_DYN | FP, true>);
       }
-    }
 #endif
-    if (epi == EPI_LN_BF16)
-      hipLaunchKernelGGL((gemm_8q_kernel<EPI_LN_BF16, 0, F_BEARLY | F_FULL | F_ONT, true>), dim3(grid), dim3(512), 0, s, a);
-    else
-      hipLaunchKernelGGL(
-          (gemm_8q_kernel<EPI_LN_GELU_BF16, 0, F_BEARLY | F_GPK | F_ONT | F_FULL | F_GSTAGE16 | F_GSTAGE | F_VOREC, true>),
-          dim3(grid), dim3(512), 0, s, a);
-    return hipGetLastError();
+      return go(gemm_8q_kernel<E, 0, FP, true>);
+    });
   }
   // the fp32 tower's split-f16 GEMMs (K' = 3K; gemm.hip launch checks the vectors)
   if (epi == EPI_F32 || epi == EPI_RESID_F32 || epi == EPI_SPLIT_GELU) {
@@ -1190,32 +1120,21 @@ hipError_t gemm_8q(const GemmArgs& a0, int epi, hipStream_t s, int cus, int mode
       return hipErrorInvalidValue;
     if (epi == EPI_SPLIT_GELU && (!a.rmax || !a.rsc_out || a.ldo != (a.o_dup ? 2 : 3) * (int64_t)a.N))
       return hipErrorInvalidValue;
+    return with_epi<EPI_F32, EPI_RESID_F32, EPI_SPLIT_GELU>(epi, [&](auto e) {
+      constexpr int E = decltype(e)::value;
 #if MICLIP_AB   // A/B (MICLIP_F32_8Q=2): the lagging M-group's epilogue beside the leading one's (F_BEARLY)
-    const char* fv = std::getenv("MICLIP_F32_8Q");
-    if (fv && std::atoi(fv) == 2 && !a.o_dup) {
-      if (epi == EPI_SPLIT_GELU) hipLaunchKernelGGL((gemm_8q_kernel<EPI_SPLIT_GELU, 0, F_BEARLY, true>), dim3(grid), dim3(512), 0, s, a);
-      else if (epi == EPI_RESID_F32) hipLaunchKernelGGL((gemm_8q_kernel<EPI_RESID_F32, 0, F_BEARLY, true>), dim3(grid), dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((gemm_8q_kernel<EPI_F32, 0, F_BEARLY, true>), dim3(grid), dim3(512), 0, s, a);
-      return hipGetLastError();
-    }
+      if (ab_env_int("MICLIP_F32_8Q", 0) == 2 && !a.o_dup) return go(gemm_8q_kernel<E, 0, F_BEARLY, true>);
 #endif
-    if (epi == EPI_SPLIT_GELU && a.o_dup) {
-      hipLaunchKernelGGL((gemm_8q_kernel<EPI_SPLIT_GELU, 0, F_ODUP, true>), dim3(grid), dim3(512), 0, s, a);
-    } else if (epi == EPI_SPLIT_GELU) {
-      hipLaunchKernelGGL((gemm_8q_kernel<EPI_SPLIT_GELU, 0, 0, true>), dim3(grid), dim3(512), 0, s, a);
-    } else if (epi == EPI_RESID_F32) {
-      hipLaunchKernelGGL((gemm_8q_kernel<EPI_RESID_F32, 0, 0, true>), dim3(grid), dim3(512), 0, s, a);
-    } else {
-      hipLaunchKernelGGL((gemm_8q_kernel<EPI_F32, 0, 0, true>), dim3(grid), dim3(512), 0, s, a);
-    }
-    return hipGetLastError();
+      if constexpr (E == EPI_SPLIT_GELU) {
+        if (a.o_dup) return go(gemm_8q_kernel<E, 0, F_ODUP, true>);
+      }
+      return go(gemm_8q_kernel<E, 0, 0, true>);
+    });
   }
   if (a.a_f16) return hipErrorInvalidValue;
   if (epi == EPI_RES16_BF16) {   // fused residual add: out = x16 (fp16), ps = row partial statistics
     if (!a.ps || mode || a.N % 64 || (a.ldo % 8)) return hipErrorInvalidValue;
-#if MICLIP_AB   // timing probes (scripts/gemm_micro.py resout500 / resproj500): 11 no statistics, 12 no x16 loads
-    const char* ab = std::getenv("MICLIP_RES_ABL");
-    const int abl = ab ? std::atoi(ab) : 0;
+#if MICLIP_AB
     // start stagger (A/B, MICLIP_RES_STAGGER=phases:ticks): workgroups start (blockIdx / 8) % phases
     // x ticks (100 MHz) late, so the CUs' epilogue x16 read bursts do not coincide chip-wide
     if (const char* st = std::getenv("MICLIP_RES_STAGGER")) {
@@ -1223,58 +1142,44 @@ hipError_t gemm_8q(const GemmArgs& a0, int epi, hipStream_t s, int cus, int mode
       const char* c = std::strchr(st, ':');
       a.stagger_ticks = c ? std::atoi(c + 1) : 0;
     }
-    if (abl == 11) hipLaunchKernelGGL((gemm_8q_kernel<EPI_RES16_BF16, 11, 0>), dim3(grid), dim3(512), 0, s, a);
-    else if (abl == 12) hipLaunchKernelGGL((gemm_8q_kernel<EPI_RES16_BF16, 12, 0>), dim3(grid), dim3(512), 0, s, a);
-    else if (abl == 13) hipLaunchKernelGGL((gemm_8q_kernel<EPI_RES16_BF16, 13, 0>), dim3(grid), dim3(512), 0, s, a);
-    else if (abl == 14) hipLaunchKernelGGL((gemm_8q_kernel<EPI_RES16_BF16, 0, F_BEARLY>), dim3(grid), dim3(512), 0, s, a);
-    else if (abl == 15) hipLaunchKernelGGL((gemm_8q_kernel<EPI_RES16_BF16, 0, F_WARM>), dim3(grid), dim3(512), 0, s, a);
-    else
+    // timing probes (scripts/gemm_micro.py resout500 / resproj500): 11 no statistics, 12 no x16 loads,
+    // 13 non-temporal x16 accesses; 14 F_BEARLY, 15 F_WARM
+    switch (ab_env_int("MICLIP_RES_ABL", 0)) {
+      case 11: return go(gemm_8q_kernel<EPI_RES16_BF16, 11, 0>);
+      case 12: return go(gemm_8q_kernel<EPI_RES16_BF16, 12, 0>);
+      case 13: return go(gemm_8q_kernel<EPI_RES16_BF16, 13, 0>);
+      case 14: return go(gemm_8q_kernel<EPI_RES16_BF16, 0, F_BEARLY>);
+      case 15: return go(gemm_8q_kernel<EPI_RES16_BF16, 0, F_WARM>);
+      default: break;
+    }
 #endif
-    hipLaunchKernelGGL((gemm_8q_kernel<EPI_RES16_BF16, 0, 0>), dim3(grid), dim3(512), 0, s, a);
-    return hipGetLastError();
+    return go(gemm_8q_kernel<EPI_RES16_BF16, 0, 0>);
   }
-#define L8Q(E, ABL_, F_) hipLaunchKernelGGL((gemm_8q_kernel<E, ABL_, F_>), dim3(grid), dim3(512), 0, s, a)
-#if MICLIP_AB   // ablation / stamp probes: A/B build only
-#define L8Q_ALL(E)                   \
-  if (mode == 0) L8Q(E, 0, 0);       \
-  else if (mode == 10) L8Q(E, 0, F_FULL); \
-  else if (mode == 2) L8Q(E, 2, 0);  \
-  else if (mode == 3) L8Q(E, 0, F_GLDS); \
-  else if (mode == 4) L8Q(E, 4, 0);  \
-  else if (mode == 9) L8Q(E, 9, 0);  \
-  else if (mode == 1) L8Q(E, 10, 0);  \
-  else return hipErrorInvalidValue;
-#else
-#define L8Q_ALL(E)                   \
-  if (mode == 0) L8Q(E, 0, 0);       \
-  else return hipErrorNotSupported;
-#endif
+  return with_epi<EPI_GELU_BF16, EPI_BF16>(epi, [&](auto e) {
+    constexpr int E = decltype(e)::value;
 #if MICLIP_AB
-  {   // A/B (MICLIP_8Q_F): epilogue flags on the plain GELU kernel (text tower / unfolded c_fc)
-    const char* fe = std::getenv("MICLIP_8Q_F");
-    const int ff = fe ? std::atoi(fe) : 0;
-    if (mode == 0 && epi == EPI_GELU_BF16 && (ff == 4 || ff == 8 || ff == 12)) {
-      if (ff == 4) L8Q(EPI_GELU_BF16, 0, F_VOREC);
-      else if (ff == 8) L8Q(EPI_GELU_BF16, 0, F_GSTAGE);
-      else L8Q(EPI_GELU_BF16, 0, F_GSTAGE | F_VOREC);
-      return hipGetLastError();
+    if (mode == 0) {   // A/B (MICLIP_8Q_F): epilogue flags on the plain kernels (text tower / unfolded c_fc)
+      const int ff = ab_env_int("MICLIP_8Q_F", 0);
+      if (ff == 4) return go(gemm_8q_kernel<E, 0, F_VOREC>);
+      if constexpr (E == EPI_GELU_BF16) {
+        if (ff == 8) return go(gemm_8q_kernel<E, 0, F_GSTAGE>);
+        if (ff == 12) return go(gemm_8q_kernel<E, 0, F_G8>);
+      }
     }
-    if (mode == 0 && epi == EPI_BF16 && ff == 4) {
-      L8Q(EPI_BF16, 0, F_VOREC);
-      return hipGetLastError();
+    switch (mode) {   // ablation / stamp probes: A/B build only
+      case 0: return go(gemm_8q_kernel<E, 0, 0>);
+      case 1: return go(gemm_8q_kernel<E, 10, 0>);
+      case 2: return go(gemm_8q_kernel<E, 2, 0>);
+      case 3: return go(gemm_8q_kernel<E, 0, F_GLDS>);
+      case 4: return go(gemm_8q_kernel<E, 4, 0>);
+      case 9: return go(gemm_8q_kernel<E, 9, 0>);
+      case 10: return go(gemm_8q_kernel<E, 0, F_FULL>);
+      default: return hipErrorInvalidValue;
     }
-  }
+#else
+    return mode == 0 ? go(gemm_8q_kernel<E, 0, 0>) : hipErrorNotSupported;
 #endif
-  if (epi == EPI_GELU_BF16) {
-    L8Q_ALL(EPI_GELU_BF16)
-  } else if (epi == EPI_BF16) {
-    L8Q_ALL(EPI_BF16)
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef L8Q_ALL
-#undef L8Q
-  return hipGetLastError();
+  });
 }
 
 }  // namespace miclip

@@ -40,8 +40,7 @@
 // K-tiles ahead across tile boundaries.  A tile's first MFMA into each
 // accumulator takes C = 0 (no zeroing pass).  Arithmetic per output element is
 // gemm_8p's (same k order, bias added after the sum), so results are bit-identical.
-#include "common.hpp"
-#include "internal.hpp"
+#include "gemm_common.hpp"
 
 namespace miclip {
 namespace {
@@ -54,22 +53,10 @@ constexpr int OFF_A0 = 0, OFF_A1 = PA, OFF_B0 = 2 * PA, OFF_B1 = 2 * PA + PB;
 constexpr int NSLOT = 3;
 constexpr int NCHUNK = 8;   // 16 x 32 drain chunks per wave tile
 
-__device__ __forceinline__ f32x2 quick_gelu2_8r(f32x2 v) {
-  const f32x2 t = v * (f32x2){-2.45546696f, -2.45546696f};   // -1.702 * log2(e)
-  f32x2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-  e = e + 1.0f;
-  return v * (f32x2){__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-}
-
 __device__ __forceinline__ void tile_coords_8r(int t, int tiles_n, int& mb, int& nb) {
   mb = t / tiles_n;
   nb = t % tiles_n;
 }
-
-template <bool V>
-struct BC8r {
-  static constexpr bool value = V;
-};
 
 // ABL (timing probes): 2 = no MFMAs, 4 = no drain work (accumulators kept live)
 template <int EPI, int ABL = 0>
@@ -171,8 +158,8 @@ __global__ __launch_bounds__(512) void gemm_8r_kernel(GemmArgs a) {
       f32x2 lo = (f32x2){pend[mi][ni][0], pend[mi][ni][1]} + (f32x2){bpend[ni].x, bpend[ni].y};
       f32x2 hi = (f32x2){pend[mi][ni][2], pend[mi][ni][3]} + (f32x2){bpend[ni].z, bpend[ni].w};
       if (EPI == EPI_GELU_BF16) {
-        lo = quick_gelu2_8r(lo);
-        hi = quick_gelu2_8r(hi);
+        lo = quick_gelu_exp2(lo);
+        hi = quick_gelu_exp2(hi);
       }
       pk[qq] = make_uint2(pack_bf16x2(lo), pack_bf16x2(hi));
     }
@@ -308,8 +295,8 @@ __global__ __launch_bounds__(512) void gemm_8r_kernel(GemmArgs a) {
           for (int ni = 0; ni < 4; ++ni) pend[mi][ni] = acc[mi][ni];
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (first) mfma_section(0, BC8r<true>{});
-      else mfma_section(0, BC8r<false>{});
+      if (first) mfma_section(0, std::bool_constant<true>{});
+      else mfma_section(0, std::bool_constant<false>{});
       // ---- phase 1: Bh1
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
@@ -330,8 +317,8 @@ __global__ __launch_bounds__(512) void gemm_8r_kernel(GemmArgs a) {
       // store, this K-tile's bias DMA, 2 x 3 DMAs and this K-tile's drain store
       wait_vm(sprev + bias_dma + scur);
       sprev = scur;
-      if (first) mfma_section(1, BC8r<true>{});
-      else mfma_section(1, BC8r<false>{});
+      if (first) mfma_section(1, std::bool_constant<true>{});
+      else mfma_section(1, std::bool_constant<false>{});
       kslot = kslot == NSLOT - 1 ? 0 : kslot + 1;
     }
     // the finished tile becomes the drain set at the next tile's first K-tile
@@ -370,24 +357,12 @@ int gemm_8r_ok(const GemmArgs& a) {
 
 // mode: 0 = default, 2 = no-MFMA probe, 4 = no-drain probe
 hipError_t gemm_8r(const GemmArgs& a, int epi, hipStream_t s, int cus, int mode) {
-  const int nt = ((a.M + BM - 1) / BM) * (a.N / BN);
-  const int grid = nt < cus ? nt : cus;
-#define L8R(E, ABL_) hipLaunchKernelGGL((gemm_8r_kernel<E, ABL_>), dim3(grid), dim3(512), 0, s, a)
-#define L8R_ALL(E)                 \
-  if (mode == 0) L8R(E, 0);        \
-  else if (mode == 2) L8R(E, 2);   \
-  else if (mode == 4) L8R(E, 4);   \
-  else return hipErrorInvalidValue;
-  if (epi == EPI_GELU_BF16) {
-    L8R_ALL(EPI_GELU_BF16)
-  } else if (epi == EPI_BF16) {
-    L8R_ALL(EPI_BF16)
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef L8R_ALL
-#undef L8R
-  return hipGetLastError();
+  const int grid = persistent_grid(tile_count(a, BM, BN), cus);
+  return with_epi<EPI_GELU_BF16, EPI_BF16>(epi, [&](auto e) {
+    return with_value<0, 2, 4>(mode, [&](auto m) {
+      return launch_kernel(gemm_8r_kernel<decltype(e)::value, decltype(m)::value>, grid, 512, s, a);
+    });
+  });
 }
 
 }  // namespace miclip

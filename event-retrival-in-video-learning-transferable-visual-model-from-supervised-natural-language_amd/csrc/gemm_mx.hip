@@ -25,11 +25,7 @@
 // LDS row image: 16-byte chunk c of row r sits in slot c ^ ((r >> 1) & 5), so
 // the two 16-byte reads of every fragment (chunks 2g, 2g+1 for lane group g)
 // hit 16 distinct bank quads per ds_read_b128 lane group (exhaustive search).
-#include <cstdlib>
-#include <type_traits>
-
-#include "common.hpp"
-#include "internal.hpp"
+#include "gemm_common.hpp"
 
 namespace miclip {
 
@@ -39,11 +35,7 @@ constexpr int MX_BK = 128;                              // k (bytes) per stage
 constexpr int MX_STAGE = 512 * MX_BK;                   // 256 A rows + 256 W rows
 constexpr int MX_SC_STAGE = 512 * 2;                    // 2 e8m0 (64-k blocks) per row per stage
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ int mx_swz(int r) { return (r >> 1) & 5; }
-
-__device__ __forceinline__ float mx_gelu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v)); }
 
 __device__ __forceinline__ void glds4(const void* gsrc, void* lds_base) {
   __builtin_amdgcn_global_load_lds((const GLB_AS void*)gsrc, (LDS_AS void*)lds_base, 4, 0, 0);
@@ -161,10 +153,10 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(GemmArgs a) {
       float amax = 0.f;
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
-        v[ni][0] = mx_gelu(acc[mi][ni][0] + bias[ni].x);
-        v[ni][1] = mx_gelu(acc[mi][ni][1] + bias[ni].y);
-        v[ni][2] = mx_gelu(acc[mi][ni][2] + bias[ni].z);
-        v[ni][3] = mx_gelu(acc[mi][ni][3] + bias[ni].w);
+        v[ni][0] = quick_gelu(acc[mi][ni][0] + bias[ni].x);
+        v[ni][1] = quick_gelu(acc[mi][ni][1] + bias[ni].y);
+        v[ni][2] = quick_gelu(acc[mi][ni][2] + bias[ni].z);
+        v[ni][3] = quick_gelu(acc[mi][ni][3] + bias[ni].w);
         amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[ni][0]), fabsf(v[ni][1])), fmaxf(fabsf(v[ni][2]), fabsf(v[ni][3]))));
       }
       amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
@@ -203,7 +195,7 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(GemmArgs a) {
         float v0 = acc[mi][ni][0] + bias[ni].x, v1 = acc[mi][ni][1] + bias[ni].y;
         float v2 = acc[mi][ni][2] + bias[ni].z, v3 = acc[mi][ni][3] + bias[ni].w;
         if (EPI == EPI_GELU_BF16) {
-          v0 = mx_gelu(v0); v1 = mx_gelu(v1); v2 = mx_gelu(v2); v3 = mx_gelu(v3);
+          v0 = quick_gelu(v0); v1 = quick_gelu(v1); v2 = quick_gelu(v2); v3 = quick_gelu(v3);
         }
         pk[q] = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
       }
@@ -237,9 +229,9 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(GemmArgs a) {
 // The MFMA computes C^T (A operand = W fragment) so lane l holds output row
 // m = l & 31 and columns 8i + 4h .. +3 (h = l >> 5) of each 32-column block:
 // permlane32_swap pairs give 16-byte bf16 row stores (T21).
-__device__ __forceinline__ int pp_swz(int x) { return (0x1320 >> (4 * x)) & 0xF; }  // {0,2,3,1}
+// (LDS image: gemm.hip's rows with swz's chunk permutation, gemm_common.hpp)
 
-// LDS reads the compiler does not see (gemm.hip lds_read_f4): with plain
+// LDS reads the compiler does not see (gemm_common.hpp lds_read_f4): with plain
 // loads from the shared array hipcc drains every in-flight LDS-DMA
 // (s_waitcnt vmcnt(0)) before the section's first read, serialising the
 // stage pipeline.  The section's lgkmcnt(0) + barrier covers the reads.
@@ -283,22 +275,9 @@ __device__ __forceinline__ int lds_u8_o(uint32_t a) {
   return v;
 }
 
-// Logical tile t -> (m-block, n-block) in groups of ng n-blocks (ng <= 0 or >= tiles_n: m-major):
-// within a group every m-block, so an XCD's contiguous run of tiles keeps its group's weight panel
-// (ng x 256 rows x K bytes of e4m3) in its 4-MB L2 (gemm_8q.hip tile_coords_8q)
-__device__ __forceinline__ void tile_coords_mx(int t, int tiles_m, int tiles_n, int ng, int& mb, int& nb) {
-  if (ng <= 0 || ng >= tiles_n) {
-    mb = t / tiles_n;
-    nb = t % tiles_n;
-    return;
-  }
-  const int per = tiles_m * ng;
-  const int gg = t / per, r = t - gg * per;
-  const int ngg = min(ng, tiles_n - gg * ng);
-  mb = r / ngg;
-  nb = gg * ng + r % ngg;
-}
-
+// Tile order (gemm_common.hpp tile_coords): n-blocks in groups of ng over every m-block, so an XCD's
+// contiguous run of tiles keeps its group's weight panel (ng x 256 rows x K bytes of e4m3) in its
+// 4-MB L2
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_mxpp_kernel(GemmArgs a) {
   typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -314,7 +293,7 @@ __global__ __launch_bounds__(512) void gemm_mxpp_kernel(GemmArgs a) {
   const int tiles_m = (a.M + BM - 1) / BM;
   const int t = xcd_remap(blockIdx.x, tiles_m * tiles_n);
   int mb_, nb_;
-  tile_coords_mx(t, tiles_m, tiles_n, a.ngroup, mb_, nb_);
+  tile_coords(t, tiles_m, tiles_n, a.ngroup, mb_, nb_);
   const int m0 = mb_ * BM, n0 = nb_ * BN;
   const int nk = a.K / SB;
   const int m_pad = (a.M + 1) & ~1;
@@ -323,7 +302,7 @@ __global__ __launch_bounds__(512) void gemm_mxpp_kernel(GemmArgs a) {
 
   // DMA: instruction j (0, 1) of wave w moves rows (w*2 + j)*16 + (lane >> 2), 4 lanes x 16 B per row
   const int lrow = lane >> 2;
-  const int lchunk = ((lane & 3) ^ pp_swz(lane >> 4)) * 16;
+  const int lchunk = ((lane & 3) ^ swz(lane >> 4)) * 16;
   const uint8_t* asrc[2];
   const uint8_t* wsrc[2];
 #pragma unroll
@@ -376,8 +355,8 @@ __global__ __launch_bounds__(512) void gemm_mxpp_kernel(GemmArgs a) {
   if (grp == 1) barrier();
 
   const int lr = lane & 31, h = lane >> 5;
-  const int rd0 = lr * SB + (((2 * h) ^ pp_swz((lr >> 2) & 3)) * 16);
-  const int rd1 = lr * SB + (((2 * h + 1) ^ pp_swz((lr >> 2) & 3)) * 16);
+  const int rd0 = lr * SB + (((2 * h) ^ swz((lr >> 2) & 3)) * 16);
+  const int rd1 = lr * SB + (((2 * h + 1) ^ swz((lr >> 2) & 3)) * 16);
   f32x16 acc[4][2];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -430,7 +409,7 @@ __global__ __launch_bounds__(512) void gemm_mxpp_kernel(GemmArgs a) {
     const float4 b = bias[ni][j >> 2];
     const float bb = (j & 3) == 0 ? b.x : (j & 3) == 1 ? b.y : (j & 3) == 2 ? b.z : b.w;
     const float v = acc[mi][ni][j] + bb;
-    return (EPI == EPI_GELU_BF16 || EPI == EPI_GELU_MX) ? mx_gelu(v) : v;
+    return (EPI == EPI_GELU_BF16 || EPI == EPI_GELU_MX) ? quick_gelu(v) : v;
   };
   if (EPI == EPI_GELU_MX) {
     // fp8 output for the next MX GEMM: the wave's 64 columns of a row are one
@@ -525,12 +504,7 @@ __global__ __launch_bounds__(512) void gemm_mxpp_kernel(GemmArgs a) {
 // group 0); the previous tile's NSTORE epilogue stores are younger than the next tile's first
 // LEAD stages and older than every later one, so the waits add them while waiting for stages
 // < LEAD; a partial last m-tile (an unknown store count) drains with vmcnt(0) instead.
-__device__ __forceinline__ float4 mx_lds_f4(const float* p) {   // (an LDS read hipcc does not see)
-  float4 v;
-  const uint32_t addr = (uint32_t)(uintptr_t)(const LDS_AS float*)p;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
+// (the bias is read through lds_read_f4: an LDS read hipcc does not see)
 
 // LEAN (round 6, A/B MICLIP_MX_PERSIST=4; measured no faster, see below): the stage loop split
 // into its head (the waits that may include the previous tile's stores), a steady part and its
@@ -572,7 +546,7 @@ __global__ __launch_bounds__(512) void gemm_mxppp_kernel(GemmArgs a) {
   auto coords = [&](int v, int& mm, int& nn) {   // grid % 8 == 0 keeps a WG's tiles on its XCD's run
     const int t = xcd_remap(v, ntiles);
     int mb, nb;
-    tile_coords_mx(t, tiles_m, tiles_n, a.ngroup, mb, nb);
+    tile_coords(t, tiles_m, tiles_n, a.ngroup, mb, nb);
     mm = mb * BM;
     nn = nb * BN;
   };
@@ -580,7 +554,7 @@ __global__ __launch_bounds__(512) void gemm_mxppp_kernel(GemmArgs a) {
   coords(vb, m0, n0);
 
   const int lrow = lane >> 2;
-  const int lchunk = ((lane & 3) ^ pp_swz(lane >> 4)) * 16;
+  const int lchunk = ((lane & 3) ^ swz(lane >> 4)) * 16;
   const int spair = (wave & 1) * 64 + lane;
   const int64_t sstage = (wave & 2) ? (int64_t)a.N * 2 : (int64_t)m_pad * 2;
   const uint8_t* asrc[2];
@@ -639,8 +613,8 @@ __global__ __launch_bounds__(512) void gemm_mxppp_kernel(GemmArgs a) {
     if (st < nk) issue(st, st);
 
   const int lr = lane & 31, h = lane >> 5;
-  const int rd0 = lr * SB + (((2 * h) ^ pp_swz((lr >> 2) & 3)) * 16);
-  const int rd1 = lr * SB + (((2 * h + 1) ^ pp_swz((lr >> 2) & 3)) * 16);
+  const int rd0 = lr * SB + (((2 * h) ^ swz((lr >> 2) & 3)) * 16);
+  const int rd1 = lr * SB + (((2 * h + 1) ^ swz((lr >> 2) & 3)) * 16);
   static_assert(RING == 4 && 96 * SB < 65536, "LEAN: ring slot by mask, read offsets in the 16-bit field");
   while (true) {
     const int nvb = vb + (int)gridDim.x;
@@ -699,7 +673,7 @@ __global__ __launch_bounds__(512) void gemm_mxppp_kernel(GemmArgs a) {
     int ln;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
     const int lr_ = ln & 31, h_ = ln >> 5;
-    const int sw_ = pp_swz((lr_ >> 2) & 3);
+    const int sw_ = swz((lr_ >> 2) & 3);
     // (three VGPRs: A's chunk-0 address, the lane's chunk-1 distance and the A-scale address; the W
     // addresses differ from the A ones by wave-uniform amounts)
     const int wcu = __builtin_amdgcn_readfirstlane(wc);
@@ -773,13 +747,13 @@ __global__ __launch_bounds__(512) void gemm_mxppp_kernel(GemmArgs a) {
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        bias[ni][i] = a.bias ? mx_lds_f4(sbias + tpar * BN + wc * WTN + ni * 32 + 8 * i + 4 * h)
+        bias[ni][i] = a.bias ? lds_read_f4(sbias + tpar * BN + wc * WTN + ni * 32 + 8 * i + 4 * h)
                              : make_float4(0.f, 0.f, 0.f, 0.f);
     auto val = [&](int mi, int ni, int j) -> float {
       const float4 b = bias[ni][j >> 2];
       const float bb = (j & 3) == 0 ? b.x : (j & 3) == 1 ? b.y : (j & 3) == 2 ? b.z : b.w;
       const float v = acc[mi][ni][j] + bb;
-      return (EPI == EPI_GELU_BF16 || EPI == EPI_GELU_MX) ? mx_gelu(v) : v;
+      return (EPI == EPI_GELU_BF16 || EPI == EPI_GELU_MX) ? quick_gelu(v) : v;
     };
     if constexpr (EPI == EPI_GELU_MX) {
       const int blk = (cn0 + wc * WTN) >> 6;
@@ -787,7 +761,7 @@ __global__ __launch_bounds__(512) void gemm_mxppp_kernel(GemmArgs a) {
       for (int mi = 0; mi < 4; ++mi) {
         const int m = cm0 + grp * WTM + mi * 32 + lr;
         // QuickGELU in stage order over the block's 32 values (each value's operations are
-        // mx_gelu's, so the result is bit-identical; consecutive transcendentals are independent,
+        // quick_gelu's, so the result is bit-identical; consecutive transcendentals are independent,
         // as gemm_8q's F_GSTAGE16)
         float v[2][16];
         float amax = 0.f;
@@ -951,8 +925,9 @@ hipError_t gemm_mx(const GemmArgs& a, int epi, hipStream_t s) {
   if (a.M <= 0) return hipSuccess;
   if (a.K % MX_BK || a.N % 256 || a.K <= 0 || !a.a_scale || !a.w_scale) return hipErrorInvalidValue;
   if ((a.lda % 16) || (a.ldw % 16) || (a.ldo % 8) || ((uintptr_t)a.out & 15)) return hipErrorInvalidValue;
-  if (epi == EPI_GELU_MX && (a.ldo % 16)) return hipErrorInvalidValue;   // 16-byte fp8 row stores
-  const int nt = ((a.M + 255) / 256) * (a.N / 256);
+  // 16-byte fp8 row stores; the output's scales must have a place
+  if (epi == EPI_GELU_MX && ((a.ldo % 16) || !a.o_scale)) return hipErrorInvalidValue;
+  const int nt = tile_count(a, 256, 256);
   // default: the ping-pong 32x32x64 kernel (needs K / 64 >= 3 stages).  A/B variants:
   // 1 the double-buffered 16x16x128 kernel; 8 the 8-phase persistent kernel (gemm_mx8q.hip:
   // bit-identical to 1, but 8-30 % slower than the ping-pong kernel at the L/14@336 shapes,
@@ -965,79 +940,34 @@ hipError_t gemm_mx(const GemmArgs& a, int epi, hipStream_t s) {
   if (a.variant != 0) return hipErrorNotSupported;   // kernel overrides exist in the A/B build only
   const bool force_dbuf = false;
 #endif
-  // persistent ping-pong (round 6; A/B MICLIP_MX_PERSIST=0 keeps one workgroup per tile): at least
+  // persistent ping-pong (round 6; A/B MICLIP_MX_PERSIST=0 keeps one workgroup per tile, 2 makes it
+  // persistent whatever K, 4 runs the lean stage loop): at least
   // one tile per CU, whole XCD runs (grid % 8 == 0) and K <= 2048.  At the configs[4] pass shapes
   // (M = 497951, scripts/mx_persist_micro.py, profiles/r06_d_mx_persist_micro.log; bit-identical):
   // c_fc -> MX-fp8 2831 vs 2947 us, qkv 1966 vs 2002, out_proj 686 vs 738; c_proj (K = 4096, a
   // 64-stage main loop) 2119 vs 2009 us, so long-K GEMMs keep one workgroup per tile
   const int cus = cu_count();
-  bool persist = nt >= cus && cus % 8 == 0 && a.K <= 2048;
-#if MICLIP_AB   // (2: persistent whatever K)
-  if (const char* pe = std::getenv("MICLIP_MX_PERSIST"))
-    persist = std::atoi(pe) == 2 ? nt >= cus && cus % 8 == 0 : persist && std::atoi(pe) != 0;   // (4: see below)
-#endif
-  if (!force_dbuf && a.K / 64 >= 3 && persist) {
-    // tile order: n-tiles in groups of 6 when there are >= 12 and a group's e4m3 panel fits 2.4 MB
-    // (an XCD's 32 concurrent tiles then hold a 1.5-MB panel at K = 1024, not the m-major walk's
-    // whole 3-4 MB, which the L2 re-fetched per m-block: FETCH 9x the operand bytes on c_fc,
-    // profiles/r06_h_fp8_gemm_traffic.json).  configs[4] shapes, bit-identical
-    // (profiles/r06_i_mx_ng.log): c_fc -> MX-fp8 2756 vs 2854 us m-major (groups of 8 2801, 4 2819,
-    // 2 2864), qkv 1961 vs 1986 (4: 2049, 2: 2070); out_proj's 4 n-tiles stay m-major
-    GemmArgs g = a;
-    const int tn = a.N / 256;
-    if (g.ngroup == 0) g.ngroup = (tn >= 12 && (int64_t)6 * 256 * a.K <= 2400000) ? 6 : -1;
-    bool lean = false;
-#if MICLIP_AB   // MICLIP_MX_NG forces the tile-order group width (-1 = m-major); MICLIP_MX_PERSIST=4
-                // runs the lean stage loop
-    if (const char* ng = std::getenv("MICLIP_MX_NG")) g.ngroup = std::atoi(ng);
-    if (const char* pe = std::getenv("MICLIP_MX_PERSIST")) lean = std::atoi(pe) == 4;
-#endif
-#define MX_PPP(E)                                                                    \
-  do {                                                                               \
-    if (lean) hipLaunchKernelGGL((gemm_mxppp_kernel<E, true>), dim3(cus), dim3(512), 0, s, g);   \
-    else hipLaunchKernelGGL((gemm_mxppp_kernel<E, false>), dim3(cus), dim3(512), 0, s, g);       \
-  } while (0)
-    switch (epi) {
-      case EPI_BF16: MX_PPP(EPI_BF16); break;
-      case EPI_GELU_BF16: MX_PPP(EPI_GELU_BF16); break;
-      case EPI_F32: MX_PPP(EPI_F32); break;
-      case EPI_GELU_MX:
-        if (!a.o_scale) return hipErrorInvalidValue;
-        MX_PPP(EPI_GELU_MX);
-        break;
-      default: return hipErrorInvalidValue;
-    }
-#undef MX_PPP
-    return hipGetLastError();
-  }
-  if (!force_dbuf && a.K / 64 >= 3) {
-    GemmArgs g = a;   // (the per-tile kernel walks m-major unless asked: A/B MICLIP_MX_NG)
-#if MICLIP_AB
-    if (const char* ng = std::getenv("MICLIP_MX_NG")) g.ngroup = std::atoi(ng);
-#endif
-    switch (epi) {
-      case EPI_BF16: hipLaunchKernelGGL(gemm_mxpp_kernel<EPI_BF16>, dim3(nt), dim3(512), 0, s, g); break;
-      case EPI_GELU_BF16: hipLaunchKernelGGL(gemm_mxpp_kernel<EPI_GELU_BF16>, dim3(nt), dim3(512), 0, s, g); break;
-      case EPI_F32: hipLaunchKernelGGL(gemm_mxpp_kernel<EPI_F32>, dim3(nt), dim3(512), 0, s, g); break;
-      case EPI_GELU_MX:
-        if (!a.o_scale) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(gemm_mxpp_kernel<EPI_GELU_MX>, dim3(nt), dim3(512), 0, s, g);
-        break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL(gemm_mx_kernel<EPI_BF16>, dim3(nt), dim3(512), 0, s, a); break;
-    case EPI_GELU_BF16: hipLaunchKernelGGL(gemm_mx_kernel<EPI_GELU_BF16>, dim3(nt), dim3(512), 0, s, a); break;
-    case EPI_F32: hipLaunchKernelGGL(gemm_mx_kernel<EPI_F32>, dim3(nt), dim3(512), 0, s, a); break;
-    case EPI_GELU_MX:
-      if (!a.o_scale) return hipErrorInvalidValue;
-      hipLaunchKernelGGL(gemm_mx_kernel<EPI_GELU_MX>, dim3(nt), dim3(512), 0, s, a);
-      break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  const int pe = ab_env_int("MICLIP_MX_PERSIST", 1);
+  const bool whole = nt >= cus && cus % 8 == 0;
+  const bool persist = pe == 2 ? whole : whole && a.K <= 2048 && pe != 0;
+  const bool staged = !force_dbuf && a.K / 64 >= 3;
+  GemmArgs g = a;
+  // tile order: n-tiles in groups of 6 when there are >= 12 and a group's e4m3 panel fits 2.4 MB
+  // (an XCD's 32 concurrent tiles then hold a 1.5-MB panel at K = 1024, not the m-major walk's
+  // whole 3-4 MB, which the L2 re-fetched per m-block: FETCH 9x the operand bytes on c_fc,
+  // profiles/r06_h_fp8_gemm_traffic.json).  configs[4] shapes, bit-identical
+  // (profiles/r06_i_mx_ng.log): c_fc -> MX-fp8 2756 vs 2854 us m-major (groups of 8 2801, 4 2819,
+  // 2 2864), qkv 1961 vs 1986 (4: 2049, 2: 2070); out_proj's 4 n-tiles stay m-major.  The per-tile
+  // kernel walks m-major unless asked.  A/B MICLIP_MX_NG forces the group width (-1 = m-major)
+  if (staged && persist && g.ngroup == 0) g.ngroup = (a.N / 256 >= 12 && (int64_t)6 * 256 * a.K <= 2400000) ? 6 : -1;
+  if (staged) g.ngroup = ab_env_int("MICLIP_MX_NG", g.ngroup);
+  return with_epi<EPI_BF16, EPI_GELU_BF16, EPI_F32, EPI_GELU_MX>(epi, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (staged && persist)
+      return pe == 4 ? launch_kernel(gemm_mxppp_kernel<E, true>, cus, 512, s, g) : launch_kernel(gemm_mxppp_kernel<E, false>, cus, 512, s, g);
+    if (staged) return launch_kernel(gemm_mxpp_kernel<E>, nt, 512, s, g);
+    return launch_kernel(gemm_mx_kernel<E>, nt, 512, s, a);
+  });
 }
 
 hipError_t quantize_mx(const uint16_t* in, int64_t ld_in, uint8_t* q, int64_t ld_q, uint8_t* sc, int rows, int K,

@@ -33,49 +33,30 @@
 //    e4m3 dword and scale-byte stores go through descriptors whose range drops
 //    rows past M (and the scale stores of lanes 16-63), with no branch, so the
 //    store count the phase-4 wait allows for is exact.
-#include "common.hpp"
-#include "internal.hpp"
+#include "gemm_common.hpp"
 
 namespace miclip {
 namespace {
 
 constexpr int BM = 256, BN = 256, BKB = 128;   // K-tile: 128 e4m3 = 128 bytes per row
-constexpr int HALF = 128 * BKB;                 // 16 KB half-tile
-constexpr int BUF = 4 * HALF;                   // 64 KB K-tile buffer
+constexpr int HALF_MX = 128 * BKB;              // 16 KB half-tile: 128 rows x 128 e4m3 (gemm_8q's HALF is 128 x 64 bf16)
+constexpr int BUF_MX = 4 * HALF_MX;             // 64 KB K-tile buffer
 constexpr int SCB = 1024;                       // a K-tile's scales: 256 A + 256 W rows x 2 B
-constexpr int H_A0 = 0, H_B0 = 1, H_B1 = 2, H_A1 = 3;
 
-typedef int v8i_q __attribute__((ext_vector_type(8)));
 typedef int v4i_q __attribute__((ext_vector_type(4)));
 
-// QuickGELU exactly as gemm_mx.hip's mx_gelu (the MX kernels' results stay bit-identical)
-__device__ __forceinline__ float quick_gelu_mx(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v)); }
-__device__ __forceinline__ f32x2 quick_gelu2_mx(f32x2 v) { return (f32x2){quick_gelu_mx(v.x), quick_gelu_mx(v.y)}; }
+// the MX kernels' QuickGELU (gemm_common.hpp quick_gelu: the results stay bit-identical to gemm_mx.hip's) on a pair
+__device__ __forceinline__ f32x2 quick_gelu2_mx(f32x2 v) { return (f32x2){quick_gelu(v.x), quick_gelu(v.y)}; }
 
-// lane id through asm: opaque to CSE/LICM, so values derived from it are rebuilt where used
-__device__ __forceinline__ int mx8q_lane_id() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
 // byte offset of this lane's 16-byte DMA piece j of a half-tile (gemm_8q's image: image row
 // (2 wave + j) * 8 + lane / 8, 16-byte slot permuted on the source)
 __device__ __forceinline__ uint32_t mx8q_dma_off(int wave, int j, bool wside, int ld) {
-  const int l = mx8q_lane_id();
+  const int l = lane_id();
   const int ir = (2 * wave + j) * 8 + (l >> 3);
   const int c = (l & 7) ^ ((j ? 4 : 0) + (l >> 4));
   const int row = wside ? (ir >> 5) * 64 + (ir & 31) : (ir >> 6) * 128 + (ir & 63);
   return (uint32_t)(row * ld + c * 16);
 }
-
-template <int P>
-struct PhMx {
-  static constexpr int value = P;
-};
-template <bool V>
-struct BoolMx {
-  static constexpr bool value = V;
-};
 
 // stores a tile's epilogue leaves in flight into the next tile's phase 4 (per wave)
 template <int EPI>
@@ -85,9 +66,9 @@ struct EpiStores {
 
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_mx8q_kernel(GemmArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * BUF + 2 * SCB + 2 * BN * 4];
-  char* ssc = smem + 2 * BUF;                       // [2][SCB]
-  float* sbias = (float*)(smem + 2 * BUF + 2 * SCB);
+  __shared__ __attribute__((aligned(16))) char smem[2 * BUF_MX + 2 * SCB + 2 * BN * 4];
+  char* ssc = smem + 2 * BUF_MX;                       // [2][SCB]
+  float* sbias = (float*)(smem + 2 * BUF_MX + 2 * SCB);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
@@ -114,7 +95,6 @@ __global__ __launch_bounds__(512) void gemm_mx8q_kernel(GemmArgs a) {
   // section) instead of 4 VGPRs held for the kernel's life: at 256 VGPRs hipcc otherwise spills
   // them and reloads them with vmcnt(0) ahead of a DMA, draining the stream.  A_m1 rows sit 64
   // rows below A_m0's and B_n1's 32 below B_n0's (soffset).
-  auto lane_id = []() { return mx8q_lane_id(); };
   auto dma_off = [&](int j, bool wside_) { return mx8q_dma_off(wave, j, wside_, wside_ ? (int)a.ldw : (int)a.lda); };
   const int a1_sofs = 64 * (int)a.lda;
   const int b1_sofs = 32 * (int)a.ldw;
@@ -137,7 +117,7 @@ __global__ __launch_bounds__(512) void gemm_mx8q_kernel(GemmArgs a) {
   };
   auto issue = [&](int h, int b) {
     const int kofs = (2 * rpp + b) * BKB;
-    char* dst = smem + b * BUF + h * HALF + (2 * wave) * 1024;
+    char* dst = smem + b * BUF_MX + h * HALF_MX + (2 * wave) * 1024;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const bool ws = !(h == H_A0 || h == H_A1);
@@ -177,7 +157,7 @@ __global__ __launch_bounds__(512) void gemm_mx8q_kernel(GemmArgs a) {
     rd1 = lfr * 128 + (((2 * lfq + 1) ^ (lfr >> 1)) << 4);
     sro = lfr * 2 + (lfq & 1);
   };
-  auto frag = [&](const char* p, v8i_q& f) {   // straight into the operand tuple's halves
+  auto frag = [&](const char* p, v8i& f) {   // straight into the operand tuple's halves
     v4i_q* h = (v4i_q*)&f;
     h[0] = *(const v4i_q*)(p + rd0);
     h[1] = *(const v4i_q*)(p + rd1);
@@ -185,7 +165,7 @@ __global__ __launch_bounds__(512) void gemm_mx8q_kernel(GemmArgs a) {
   // scale bytes: plain (compiler-visible) LDS byte loads, one per VGPR (opsel 0), at the lane's
   // row / k-block offset sro rebuilt per phase with the fragment offsets
   auto sbyte = [&](int off) -> int { return (int)*((const uint8_t*)ssc + off + sro); };
-  v8i_q fa[4], fb0[2], fb1[2];
+  v8i fa[4], fb0[2], fb1[2];
   int sa[4], sw0[2], sw1[2];
   auto read_a = [&](const char* half, auto bc, auto mhc) {
     constexpr int b = decltype(bc)::value, mh = decltype(mhc)::value;
@@ -199,7 +179,7 @@ __global__ __launch_bounds__(512) void gemm_mx8q_kernel(GemmArgs a) {
     sa[2] = sbyte(ao + 64);
     sa[3] = sbyte(ao + 96);
   };
-  auto read_b = [&](const char* half, auto bc, auto nhc, v8i_q (&fb)[2], int (&sw)[2]) {
+  auto read_b = [&](const char* half, auto bc, auto nhc, v8i (&fb)[2], int (&sw)[2]) {
     constexpr int b = decltype(bc)::value, nh = decltype(nhc)::value;
     frag(half + (wc * 32) * 128, fb[0]);
     frag(half + (wc * 32 + 16) * 128, fb[1]);
@@ -337,7 +317,7 @@ __global__ __launch_bounds__(512) void gemm_mx8q_kernel(GemmArgs a) {
     constexpr bool FIRST = decltype(firstc)::value, LAST = decltype(lastc)::value;
     constexpr int b = P <= 4 ? 0 : 1;
     constexpr int q = (P - 1) & 3;
-    const char* rbuf = smem + b * BUF;
+    const char* rbuf = smem + b * BUF_MX;
     if (P == 1) {
       // a tile's first pair: the odd K-tile's scales, oldest of the phase (older than the
       // previous tile's stores); the last pair read them last in phase 7 (no phase-8 re-read)
@@ -352,14 +332,14 @@ __global__ __launch_bounds__(512) void gemm_mx8q_kernel(GemmArgs a) {
     }
     if (!(LAST && P == 8)) frag_offsets();
     if (q == 0) {
-      read_a(rbuf + H_A0 * HALF, PhMx<b>{}, PhMx<0>{});
-      read_b(rbuf + H_B0 * HALF, PhMx<b>{}, PhMx<0>{}, fb0, sw0);
+      read_a(rbuf + H_A0 * HALF_MX, Phase<b>{}, Phase<0>{});
+      read_b(rbuf + H_B0 * HALF_MX, Phase<b>{}, Phase<0>{}, fb0, sw0);
     } else if (q == 1) {
-      read_b(rbuf + H_B1 * HALF, PhMx<b>{}, PhMx<1>{}, fb1, sw1);
+      read_b(rbuf + H_B1 * HALF_MX, Phase<b>{}, Phase<1>{}, fb1, sw1);
     } else if (q == 2) {
-      read_a(rbuf + H_A1 * HALF, PhMx<b>{}, PhMx<1>{});
+      read_a(rbuf + H_A1 * HALF_MX, Phase<b>{}, Phase<1>{});
     } else if (!(LAST && P == 8)) {
-      read_b(rbuf + H_B0 * HALF, PhMx<b>{}, PhMx<0>{}, fb0, sw0);
+      read_b(rbuf + H_B0 * HALF_MX, Phase<b>{}, Phase<0>{}, fb0, sw0);
     }
     __builtin_amdgcn_sched_barrier(0);
     if (P == 2 && !FIRST) { issue_sc(1); issue(H_B0, 1); }   // two phases after phase 8's read
@@ -420,14 +400,14 @@ __global__ __launch_bounds__(512) void gemm_mx8q_kernel(GemmArgs a) {
     barrier();
   };
   auto pair = [&](auto firstc, auto lastc) {
-    phase(PhMx<1>{}, firstc, lastc);
-    phase(PhMx<2>{}, firstc, lastc);
-    phase(PhMx<3>{}, firstc, lastc);
-    phase(PhMx<4>{}, firstc, lastc);
-    phase(PhMx<5>{}, firstc, lastc);
-    phase(PhMx<6>{}, firstc, lastc);
-    phase(PhMx<7>{}, firstc, lastc);
-    phase(PhMx<8>{}, firstc, lastc);
+    phase(Phase<1>{}, firstc, lastc);
+    phase(Phase<2>{}, firstc, lastc);
+    phase(Phase<3>{}, firstc, lastc);
+    phase(Phase<4>{}, firstc, lastc);
+    phase(Phase<5>{}, firstc, lastc);
+    phase(Phase<6>{}, firstc, lastc);
+    phase(Phase<7>{}, firstc, lastc);
+    phase(Phase<8>{}, firstc, lastc);
   };
 
   // ---- prologue: tile 0's bias, the even K-tile's scales and halves, the odd A_m0 / B_n1 of pair 0
@@ -455,9 +435,9 @@ __global__ __launch_bounds__(512) void gemm_mx8q_kernel(GemmArgs a) {
       int nm0;
       coords(v + G, nm0, nxt_n0);
     }
-    pair(BoolMx<true>{}, BoolMx<false>{});
-    for (int pp = 1; pp < npairs - 1; ++pp) pair(BoolMx<false>{}, BoolMx<false>{});
-    pair(BoolMx<false>{}, BoolMx<true>{});
+    pair(std::bool_constant<true>{}, std::bool_constant<false>{});
+    for (int pp = 1; pp < npairs - 1; ++pp) pair(std::bool_constant<false>{}, std::bool_constant<false>{});
+    pair(std::bool_constant<false>{}, std::bool_constant<true>{});
     pm0 = cm0;
     pn0 = cn0;
     ppar = cpar;
@@ -479,15 +459,9 @@ int gemm_mx8q_ok(const GemmArgs& a, int epi) {
 }
 
 hipError_t gemm_mx8q(const GemmArgs& a, int epi, hipStream_t s, int cus) {
-  const int nt = ((a.M + BM - 1) / BM) * (a.N / BN);
-  const int grid = nt < cus ? nt : cus;
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL(gemm_mx8q_kernel<EPI_BF16>, dim3(grid), dim3(512), 0, s, a); break;
-    case EPI_GELU_BF16: hipLaunchKernelGGL(gemm_mx8q_kernel<EPI_GELU_BF16>, dim3(grid), dim3(512), 0, s, a); break;
-    case EPI_GELU_MX: hipLaunchKernelGGL(gemm_mx8q_kernel<EPI_GELU_MX>, dim3(grid), dim3(512), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  const int grid = persistent_grid(tile_count(a, BM, BN), cus);
+  return with_epi<EPI_BF16, EPI_GELU_BF16, EPI_GELU_MX>(
+      epi, [&](auto e) { return launch_kernel(gemm_mx8q_kernel<decltype(e)::value>, grid, 512, s, a); });
 }
 
 }  // namespace miclip

@@ -29,8 +29,7 @@
 // rows, one slot) then covers all 16 bank slots (conflict-free); the DMA
 // applies the same permutation on its source address (the LDS side of an
 // LDS-DMA is lane-linear, guide §5.4 rule 21).
-#include "common.hpp"
-#include "internal.hpp"
+#include "gemm_common.hpp"
 
 namespace miclip {
 namespace {
@@ -39,37 +38,6 @@ constexpr int BM = 256, BN = 256, BKW = 64;
 constexpr int PART = 256 * BKW * 2;      // 32 KB: one operand's rows of a stage
 constexpr int STAGE = 2 * PART;          // 64 KB
 constexpr int NSTORE = 32;               // epilogue store instructions per wave (full tile)
-
-__device__ __forceinline__ float quick_gelu_w4(float v) {
-  return v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v));
-}
-
-__device__ __forceinline__ float4 lds_read_f4_w4(const float* p) {
-  float4 v;
-  const uint32_t addr = (uint32_t)(uintptr_t)(const LDS_AS float*)p;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-
-// logical tile t -> (m-block, n-block): n-blocks walked in groups of ng
-// (ng <= 0 or >= tiles_n: m-major raster), as gemm.hip tile_coords
-__device__ __forceinline__ void tile_coords_w4(int t, int tiles_m, int tiles_n, int ng, int& mb, int& nb) {
-  if (ng <= 0 || ng >= tiles_n) {
-    mb = t / tiles_n;
-    nb = t % tiles_n;
-    return;
-  }
-  const int per = tiles_m * ng;
-  const int gg = t / per, r = t - gg * per;
-  const int ngg = min(ng, tiles_n - gg * ng);
-  mb = r / ngg;
-  nb = gg * ng + r % ngg;
-}
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
 
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_w4_kernel(GemmArgs a) {
@@ -88,7 +56,7 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(GemmArgs a) {
   auto coords = [&](int v, int& mm, int& nn) {
     const int t = xcd_remap(v, ntiles);
     int mb, nb;
-    tile_coords_w4(t, tiles_m, tiles_n, a.ngroup, mb, nb);
+    tile_coords(t, tiles_m, tiles_n, a.ngroup, mb, nb);
     mm = mb * BM;
     nn = nb * BN;
   };
@@ -210,7 +178,7 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(GemmArgs a) {
     float4 bias[8];
 #pragma unroll
     for (int ni = 0; ni < 8; ++ni)
-      bias[ni] = a.bias ? lds_read_f4_w4(sbias + cpar * BN + 128 * wn + ni * 16 + 4 * gq)
+      bias[ni] = a.bias ? lds_read_f4(sbias + cpar * BN + 128 * wn + ni * 16 + 4 * gq)
                         : make_float4(0.f, 0.f, 0.f, 0.f);
     const bool full = cm0 + BM <= a.M;
 #pragma unroll
@@ -225,7 +193,7 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(GemmArgs a) {
           float v0 = acc[mi][ni][0] + bias[ni].x, v1 = acc[mi][ni][1] + bias[ni].y;
           float v2 = acc[mi][ni][2] + bias[ni].z, v3 = acc[mi][ni][3] + bias[ni].w;
           if (EPI == EPI_GELU_BF16) {
-            v0 = quick_gelu_w4(v0); v1 = quick_gelu_w4(v1); v2 = quick_gelu_w4(v2); v3 = quick_gelu_w4(v3);
+            v0 = quick_gelu(v0); v1 = quick_gelu(v1); v2 = quick_gelu(v2); v3 = quick_gelu(v3);
           }
           pk[q] = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
         }
@@ -254,12 +222,9 @@ int gemm_w4_ok(const GemmArgs& a) {
 }
 
 hipError_t gemm_w4(const GemmArgs& a, int epi, hipStream_t s, int cus) {
-  const int nt = ((a.M + BM - 1) / BM) * (a.N / BN);
-  const int grid = nt < cus ? nt : cus;
-  if (epi == EPI_GELU_BF16) hipLaunchKernelGGL(gemm_w4_kernel<EPI_GELU_BF16>, dim3(grid), dim3(256), 0, s, a);
-  else if (epi == EPI_BF16) hipLaunchKernelGGL(gemm_w4_kernel<EPI_BF16>, dim3(grid), dim3(256), 0, s, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  const int grid = persistent_grid(tile_count(a, BM, BN), cus);
+  return with_epi<EPI_GELU_BF16, EPI_BF16>(
+      epi, [&](auto e) { return launch_kernel(gemm_w4_kernel<decltype(e)::value>, grid, 256, s, a); });
 }
 
 }  // namespace miclip

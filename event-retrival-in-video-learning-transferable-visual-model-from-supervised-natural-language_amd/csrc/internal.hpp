@@ -56,6 +56,27 @@ __device__ __forceinline__ int64_t mx_scale_index(int64_t r, int b, int64_t rows
   return ((int64_t)(b >> 1) * rows_pad + r) * 2 + (b & 1);
 }
 
+// Split-f16 operands of the fp32 tower (split2h_rows below; the arithmetic is described in
+// precise.hip), shared by their producers: precise.hip's kernels and the EPI_SPLIT_GELU epilogues of
+// gemm.hip / gemm_8q.hip.  A row scaled by s = 2^e, max |x s| in [2^13, 2^14), splits as
+// x s = x1 + x2 + r with x1 = f16(x s), x2 = f16(x s - x1).
+__device__ __forceinline__ int split_exp(float mx) {   // s = 2^e: mx * s in [2^13, 2^14)
+  if (!(mx > 0.f) || !__builtin_isfinite(mx)) return 0;   // zero / non-finite row: unscaled
+  int ex;
+  (void)frexpf(mx, &ex);                                 // mx = f 2^ex, f in [0.5, 1)
+  const int e = 14 - ex;
+  return e > 126 ? 126 : (e < -126 ? -126 : e);          // 1 / s stays a normal float
+}
+__device__ __forceinline__ void split2h(float xs, _Float16& x1, _Float16& x2) {
+  x1 = (_Float16)xs;
+  const float f1 = (float)x1;
+  // inf / NaN (only in rows left unscaled): carried by x1 alone
+  x2 = __builtin_isfinite(f1) ? (_Float16)(xs - f1) : (_Float16)0.f;
+}
+// QuickGELU of the fp32 tower's f32 epilogues (expf and a true division, not the bf16 kernels'
+// hardware forms of gemm_common.hpp)
+__device__ __forceinline__ float quick_gelu_f32(float v) { return v * (1.0f / (1.0f + expf(-1.702f * v))); }
+
 struct GemmArgs {
   const uint16_t* A;  // [M, K] bf16, row stride lda
   const uint16_t* W;  // [N, K] bf16 (nn.Linear layout), row stride ldw
@@ -68,7 +89,7 @@ struct GemmArgs {
   int variant;  // main-loop schedule (0 = default choice; see gemm.hip)
   const uint8_t *a_scale, *w_scale;  // MX-fp8 GEMM: e8m0 per 64 k, stage-major [K/128][rows_pad][2] (gemm_mx.hip)
   uint8_t* o_scale;                  // EPI_GELU_MX: scales of the fp8 output (same layout, rows = M)
-  int ngroup;   // tile order: n-blocks per group (0 = m-major raster; gemm.hip tile_coords)
+  int ngroup;   // tile order: n-blocks per group (0 = m-major raster; gemm_common.hpp tile_coords)
   // Fused patch gather (gemm.hip, bf16 A only): patch_R > 0 makes A the bf16
   // NCHW pixels [B,3,R,R] and row m the patch (m / G^2, m % G^2) of a P = 32
   // grid (K = 3*32*32, one 32-pixel image-row segment per BK = 32 stage), so

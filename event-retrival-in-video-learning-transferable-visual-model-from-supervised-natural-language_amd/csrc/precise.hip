@@ -179,22 +179,8 @@ __global__ __launch_bounds__(256) void split6_kernel(const float* __restrict__ x
 // Against the split-bf16 form (split6_rows, K' = 6K) that halves the MFMA work and the operand
 // bytes at the same accuracy (numpy simulation at K = 768 / 3072: 7.1e-7 / 4.7e-7 of max |ref|
 // for f16 x 3 against 3.2e-7 / 5.8e-7 for bf16 x 6).
-__device__ __forceinline__ int split_exp(float mx) {   // s = 2^e: mx * s in [2^13, 2^14)
-  if (!(mx > 0.f) || !__builtin_isfinite(mx)) return 0;   // zero / non-finite row: unscaled
-  int ex;
-  (void)frexpf(mx, &ex);                                 // mx = f 2^ex, f in [0.5, 1)
-  const int e = 14 - ex;
-  return e > 126 ? 126 : (e < -126 ? -126 : e);          // 1 / s stays a normal float
-}
-
-__device__ __forceinline__ void split2h(float xs, _Float16& x1, _Float16& x2) {
-  x1 = (_Float16)xs;
-  const float f1 = (float)x1;
-  // inf / NaN (only in rows left unscaled): carried by x1 alone
-  x2 = __builtin_isfinite(f1) ? (_Float16)(xs - f1) : (_Float16)0.f;
-}
-
-__device__ __forceinline__ float quick_gelu_f32(float v) { return v * (1.0f / (1.0f + expf(-1.702f * v))); }
+// (split_exp, split2h and the f32 epilogues' quick_gelu_f32 live in internal.hpp: the GEMMs'
+// EPI_SPLIT_GELU epilogues use them too)
 
 __device__ __forceinline__ float absmax4(float m, float4 v) {
   return fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));

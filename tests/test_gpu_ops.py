@@ -89,6 +89,48 @@ def test_gemm_8phase_schedules_bit_identical(gpu, M, N, K, epi):
     assert rc == -3 and b"A/B build" in N_.lib().mi_last_error()      # MI_ERR_UNSUPPORTED
 
 
+AB_VARIANTS = (1, 2, 3, 4, 5, 6, 16, 17, 18, 19, 20, 42, 62, 70, 82, 97, 98, 99, 110, 113, 115, 116, 117, 125, 131,
+               132)
+
+
+@pytest.mark.parametrize("epi", [0, 1])
+def test_gemm_ab_variants_run(gpu, epi):
+    """Every A/B schedule variant with a real output (gemm.hip's variant dispatch) computes the GEMM:
+    each against torch fp32 at test_gemm's bf16 tolerance; v110, v113 and the product default also
+    bit-identical to v98.  One shape: five M-tiles with a partial last one, three N-tiles (a group
+    width of 2 leaves a ragged last group), two 128-k pairs (the shortest K of the 8-phase kernels),
+    M >= 1024 so the 256 x 256 ping-pong paths are taken.  The probe / ablation numbers (8, 31-35,
+    87, 88, 91-96, 111, 112, 114) write no or wrong output by design and are not run."""
+    import torch
+    N_ = _lib()
+    AB = N_.lib_ab()
+    M, N, K = 1100, 768, 256
+    g = torch.Generator(device="cpu").manual_seed(1100 + epi)
+    A = (torch.rand(M, K, generator=g) * 2 - 1).bfloat16().to(gpu)
+    W = ((torch.rand(N, K, generator=g) * 2 - 1) * K ** -0.5).bfloat16().to(gpu)
+    bias = torch.randn(N, generator=g).float().to(gpu)
+    ref = A.float() @ W.float().t() + bias
+    if epi == 1:
+        ref = ref * torch.sigmoid(1.702 * ref)
+    tol = 2e-2 * max(1.0, ref.abs().max().item())
+    outs = {}
+    for v in AB_VARIANTS + (0,):
+        out = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=gpu)
+        L = N_.lib() if v == 0 else AB            # v = 0: the product library's default dispatch
+        rc = L.mi_op_gemm(A.data_ptr(), W.data_ptr(), bias.data_ptr(), out.data_ptr(), M, N, K, epi | (v << 8),
+                          _stream())
+        if rc:
+            raise N_.MiClipError(f"gemm v{v}: {L.mi_last_error()}")
+        outs[v] = out
+    torch.cuda.synchronize()
+    errs = {v: (o.float() - ref).abs().max().item() for v, o in outs.items()}
+    print("max err per variant:", errs, "tol", tol)
+    bad = {v: e for v, e in errs.items() if not e < tol}      # (a NaN left in the output fails too)
+    assert not bad, f"variants outside tol {tol}: {bad}"
+    for v in (110, 113, 0):
+        assert torch.equal(outs[v], outs[98]), f"v{v} differs from v98"
+
+
 def test_gemm_asymmetric_identity(gpu):
     """A = I with an asymmetric W catches a transposed C write (guide §3)."""
     import torch
