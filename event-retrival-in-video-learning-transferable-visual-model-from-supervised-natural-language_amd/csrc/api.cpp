@@ -295,25 +295,16 @@ static hipError_t ws_release(mi_clip* c, hipStream_t s) {
   return hipEventRecord(c->ws_evt, s);
 }
 
-// A/B switches (MICLIP_* environment overrides of the measured defaults): the A/B build
-// (scripts/ab, MICLIP_AB=1) reads them on every call, so that a test can switch them within one
-// process; the product library always runs the defaults.
-static int ab_int(const char* name, int dflt) {
-#if MICLIP_AB
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-#else
-  (void)name;
-  return dflt;
-#endif
-}
+// A/B switches (MICLIP_* environment overrides of the measured defaults) are read through
+// ab_env_int (internal.hpp): the A/B build (scripts/ab, MICLIP_AB=1) reads them on every call, so
+// that a test can switch them within one process; the product library always runs the defaults.
 
 // The fp32 tower's GEMMs (run_tower_f32): 3 = split-f16 operands on the f16 MFMA (the
 // default since round 5, K' = 3K), 6 = split-bf16 operands (round 4, K' = 6K), 0 = the exact-f32
 // MFMA GEMM (precise.hip gemm_f32).  MICLIP_F32_SPLIT selects one in the A/B build (read when a
 // context is created: the weight copies are built for the mode).
 static int f32_gemm_mode() {
-  const int v = ab_int("MICLIP_F32_SPLIT", 3);
+  const int v = ab_env_int("MICLIP_F32_SPLIT", 3);
   return v == 0 || v == 6 ? v : 3;
 }
 
@@ -692,7 +683,7 @@ int mi_clip_reserve(mi_clip* c, int64_t image_chunk, int64_t text_chunk) {
 }
 
 // GEMM main-loop schedule (gemm.hip): MICLIP_GEMM_VARIANT overrides the default.
-static int gemm_variant() { return ab_int("MICLIP_GEMM_VARIANT", 0); }
+static int gemm_variant() { return ab_env_int("MICLIP_GEMM_VARIANT", 0); }
 
 // Per-GEMM schedule overrides for A/B runs of the whole encoder
 // (MICLIP_GEMM_VARIANT_{QKV,OUT,FC,PROJ}; 0 = MICLIP_GEMM_VARIANT / default).
@@ -700,7 +691,7 @@ enum { GV_QKV = 0, GV_OUT = 1, GV_FC = 2, GV_PROJ = 3 };
 static int gemm_variant_for(int which) {
   static const char* names[4] = {"MICLIP_GEMM_VARIANT_QKV", "MICLIP_GEMM_VARIANT_OUT", "MICLIP_GEMM_VARIANT_FC",
                                  "MICLIP_GEMM_VARIANT_PROJ"};
-  return ab_int(names[which], 0);
+  return ab_env_int(names[which], 0);
 }
 
 static GemmArgs with_variant(GemmArgs g, int which) {
@@ -722,14 +713,14 @@ static GemmArgs gargs(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t
 // Vision residual stream storage: fp16 after the first residual add (2 B
 // instead of 4 per element on each of the 24 residual LayerNorms' read and
 // write); MICLIP_RESID16=0 keeps it f32 (A/B, parity comparisons).
-static int resid16() { return ab_int("MICLIP_RESID16", 1) != 0; }
+static int resid16() { return ab_env_int("MICLIP_RESID16", 1) != 0; }
 // Patch embedding reads the bf16 pixels straight from the GEMM's A-operand DMA
 // (B/32: one 32-pixel row segment per k stage) instead of through an im2col
 // buffer; MICLIP_PATCH_FUSED=0 keeps the im2col pass (A/B).
-static int patch_fused() { return ab_int("MICLIP_PATCH_FUSED", 1) != 0; }
+static int patch_fused() { return ab_env_int("MICLIP_PATCH_FUSED", 1) != 0; }
 // The first block's ln_1 fused into the vision embedding kernel (bf16 tower);
 // MICLIP_EMBED_LN1=0 keeps the separate LayerNorm pass (A/B).
-static int embed_ln1() { return ab_int("MICLIP_EMBED_LN1", 1) != 0; }
+static int embed_ln1() { return ab_env_int("MICLIP_EMBED_LN1", 1) != 0; }
 // xmode of a layer's first residual_ln: the f32 stream from ln_pre is converted at layer 0
 static int xmode_at(int r16, size_t l) { return r16 ? (l == 0 ? 1 : 2) : 0; }
 
@@ -775,7 +766,7 @@ static int run_tower(mi_clip* c, const std::vector<Layer>& layers, int B, int S,
 // up: configs[2] 16.25 -> 16.32 s per step, profiles/r04_v_config2.json).  With the fused residual
 // it pays at L/14 too: 6566 frames/s against 6160 unfolded and 6107 folded without the fusion
 // (10k frames x 256 queries, profiles/r04_al_l14_fold.log).
-static int lnfold(int W) { return ab_int("MICLIP_LNFOLD", W <= 1024) != 0; }
+static int lnfold(int W) { return ab_env_int("MICLIP_LNFOLD", W <= 1024) != 0; }
 
 static GemmArgs ln_args(mi_clip* c, const uint16_t* wf, const float* sv, const float* cv, void* out, int N, int M,
                         int W) {
@@ -793,7 +784,7 @@ static GemmArgs ln_args(mi_clip* c, const uint16_t* wf, const float* sv, const f
 // element) instead of writing delta and residual_stats re-reading it (8 B).  The partials live
 // in the h buffer, which the folded tower does not otherwise use.  MICLIP_RESFUSE=0 keeps the
 // separate residual_stats pass (A/B).
-static int resfuse() { return ab_int("MICLIP_RESFUSE", 1) != 0; }
+static int resfuse() { return ab_env_int("MICLIP_RESFUSE", 1) != 0; }
 
 // Bump allocator over a workspace buffer that is dead while it is borrowed (qkv after attention;
 // h in the towers that do not write it): sub-buffers on 256-byte boundaries, checked against the
@@ -848,7 +839,7 @@ static int gemm_residual(mi_clip* c, const uint16_t* A, int64_t lda, const uint1
 // values of the full pass's CLS rows bit for bit (each GEMM row's arithmetic does not depend on
 // the rows beside it).  Needs the 8-phase kernel's 256 rows (B >= 256); the compact rows live in
 // the qkv buffer, dead after attention.  MICLIP_CLS_LAST=0 (A/B) runs the full block.
-static int cls_last() { return ab_int("MICLIP_CLS_LAST", 1) != 0; }
+static int cls_last() { return ab_env_int("MICLIP_CLS_LAST", 1) != 0; }
 
 // The decision, one for every tower: the last layer, whole 256-row tiles of CLS rows, and the
 // tower's own precondition `pre`
@@ -936,7 +927,7 @@ static int run_tower_fold(mi_clip* c, const std::vector<Layer>& layers, int B, i
     };
     if (cls) MI_TRY(in_proj_cls(c, B, S, W, c->rs, 8, &GemmArgs::rs, EPI_LN_BF16, s, in_proj));
     else HIP_TRY(gemm_bf16(in_proj(0, 3 * W, M, 1), EPI_LN_BF16, s));
-    HIP_TRY(attention(c->qkv, c->att, B, S, W, cls ? 0x800 : 0, s));   // (cls: the CLS queries' tile only)
+    HIP_TRY(attention(c->qkv, c->att, B, S, W, cls ? ATT_Q0_ONLY : 0, s));   // (cls: the CLS queries' tile only)
     if (cls) return last_block_cls(c, L, B, S, W, xpost, post_stride, s);
     if (fuse) {
       MI_TRY(gemm_residual(c, c->att, W, L.w_out, L.b_out, c->x, M, W, W, s));
@@ -1030,12 +1021,12 @@ static int run_tower_f32_split2h(mi_clip* c, const std::vector<Layer>& layers, i
   //               epilogue (o_dup), bit-identical.  MICLIP_F32_DUP=0 keeps the full layout everywhere
   //               (a mask: 1 ln_1's split, 2 attention's, 4 ln_2's, 8 c_fc's output)
   //   dup_on      ... and MICLIP_F32_8Q=0 with it (the ping-pong kernel reads the full layout)
-  const int dmask_env = ab_int("MICLIP_F32_DUP", 15);
+  const int dmask_env = ab_env_int("MICLIP_F32_DUP", 15);
   const struct {
     bool fuse_split, att_fused, dup_on;
     int dmask;
-  } sw = {ab_int("MICLIP_F32_FUSED_SPLIT", 1) != 0, ab_int("MICLIP_F32_ATTN_FUSED", 1) != 0,
-          dmask_env != 0 && ab_int("MICLIP_F32_8Q", 1) != 0, dmask_env};
+  } sw = {ab_env_int("MICLIP_F32_FUSED_SPLIT", 1) != 0, ab_env_int("MICLIP_F32_ATTN_FUSED", 1) != 0,
+          dmask_env != 0 && ab_env_int("MICLIP_F32_8Q", 1) != 0, dmask_env};
   uint16_t* a3o = a3 + (int64_t)M * 3 * W;
   float* rsc_o = rsc + c->rsc_rows;
   float* rmax = rsc + 2 * c->rsc_rows;
@@ -1076,10 +1067,10 @@ static int run_tower_f32_split2h(mi_clip* c, const std::vector<Layer>& layers, i
     // CLS rows in that block)
     bool da = (sw.dmask & 2) && fuse_att && (cls ? dup_ok(B, W, W, S) : dup_ok(M, W, W));
     if (fuse_att)
-      HIP_TRY(attention_f32_split(qkv, rmax, L.v_bw, L.v_bb, a3, da ? 2 : 0, rsc, B, S, W, causal | (cls ? 0x800 : 0),
+      HIP_TRY(attention_f32_split(qkv, rmax, L.v_bw, L.v_bb, a3, da ? 2 : 0, rsc, B, S, W, causal | (cls ? ATT_Q0_ONLY : 0),
                                   s));
     else
-      HIP_TRY(attention_f32(qkv, att, B, S, W, causal | (cls ? 0x800 : 0), s));   // (cls: the CLS queries' block)
+      HIP_TRY(attention_f32(qkv, att, B, S, W, causal | (cls ? ATT_Q0_ONLY : 0), s));   // (cls: the CLS queries' block)
     ClsRows r = {att, nullptr, c->x};   // att [B][W] f32 (room only with fuse_att), x [B][W] f32
     float* rsc_a = rsc;   // the scales of out_proj's operand rows
     if (cls) {
@@ -1219,7 +1210,7 @@ static int image_chunk_f32(mi_clip* c, const void* px, int in_dtype, int nb, con
   // conv1 as a split-f16 GEMM (rows remapped past CLS); its operand straight from the pixels where
   // the patch rows are float4-aligned (P % 4 == 0: B/32, B/16; MICLIP_IM2COL_SPLIT=0 in the A/B
   // build keeps im2col_f32 + split2h_rows)
-  const bool fused = ab_int("MICLIP_IM2COL_SPLIT", 1) != 0 && P % 4 == 0 && R % 4 == 0 && c->Kp32 == 3 * P * P &&
+  const bool fused = ab_env_int("MICLIP_IM2COL_SPLIT", 1) != 0 && P % 4 == 0 && R % 4 == 0 && c->Kp32 == 3 * P * P &&
                      c->Kp32 <= 4096 && ((uintptr_t)px & 15) == 0;
   const bool split3 = c->conv_h3 && c->a6 && c->rsc;
   if (!(split3 && fused)) HIP_TRY(im2col_f32(px, in_dtype == MI_BF16, patches, nb, R, P, c->Kp32, s));
@@ -1685,8 +1676,8 @@ int mi_op_gemm_residual(void* x16, int64_t ldx, const void* A, int64_t lda, cons
 
 int mi_op_attention(const void* qkv, void* out, int32_t B, int32_t S, int32_t W, int32_t causal, void* stream) {
   if (!qkv || !out || B < 0 || S < 1) return fail(MI_ERR_ARG, "mi_op_attention: bad arguments");
-  if (W % 64 || S > 640 || (causal & ~0x301)) return fail(MI_ERR_UNSUPPORTED, "mi_op_attention: W %% 64 == 0 and S <= 640");
-  if ((causal & 0x100) && !MICLIP_AB) return fail(MI_ERR_UNSUPPORTED, "mi_op_attention: the one-wave kernel (bit 8) is in the A/B build");
+  if (W % 64 || S > 640 || (causal & ~(ATT_CAUSAL | ATT_ONE_WAVE | ATT_STREAM))) return fail(MI_ERR_UNSUPPORTED, "mi_op_attention: W %% 64 == 0 and S <= 640");
+  if ((causal & ATT_ONE_WAVE) && !MICLIP_AB) return fail(MI_ERR_UNSUPPORTED, "mi_op_attention: the one-wave kernel (bit 8) is in the A/B build");
   HIP_TRY(attention((const uint16_t*)qkv, (uint16_t*)out, B, S, W, causal, (hipStream_t)stream));
   return MI_OK;
 }

@@ -14,6 +14,122 @@ namespace miclip {
 
 namespace {
 
+// ------------------------------------------------------- shared device pieces
+// (the only copy of each; the kernels below describe where they use them)
+
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+
+// compile-time tile counts handed to the kernels' generic lambdas (bools travel as std::bool_constant)
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+constexpr float sl2 = 0.125f * 1.4426950408889634f;   // head_dim^-0.5 * log2(e): scores to the log2 domain
+constexpr float RESCALE = 8.0f;                       // lazy-rescale threshold (log2 units)
+
+// A query row's max / sum over the lanes that hold it.  16x16 C layout: the row is on lane fr of
+// each of the four 16-lane groups -> permlane16 then permlane32 swap; 32x32 layout (P16 = false): on
+// lane r of both wave halves -> the permlane32 swap alone.
+template <bool P16 = true>
+__device__ __forceinline__ float group_max(float v) {
+  if (P16) {
+    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+  }
+  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+}
+template <bool P16 = true>
+__device__ __forceinline__ float group_sum(float v) {
+  if (P16) {
+    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+  }
+  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
+}
+
+// Lazy rescale of the online softmax (log2 domain): the running max m only moves, and l and the
+// accumulators o are only rescaled, when the chunk max cmu exceeds m by more than 2^RESCALE, so
+// P <= 256 and the result is exact after the final 1 / l.  o: f32x4[4] (16x16) or f32x16[2] (32x32).
+template <class V, int N>
+__device__ __forceinline__ void lazy_rescale(float& m, float& l, V (&o)[N], float cmu) {
+  if (cmu > m + RESCALE) {
+    const float alpha = __builtin_amdgcn_exp2f(m - cmu);
+    l *= alpha;
+#pragma unroll
+    for (int i = 0; i < N; ++i) o[i] *= alpha;
+    m = cmu;
+  }
+}
+
+// Q fragments (B operand of S^T = K Q^T) of a 16-row query tile for the 16x16x32 MFMA: lane (fr, g)
+// holds head dims 32 s + 8 g .. + 7 of row 16 tile + fr, rows past S clamped.  (attention_r32_kernel's
+// two loads of a 32-row block stay written out: through a helper its two-phase instantiation changed.)
+__device__ __forceinline__ void load_q16(const uint16_t* qb, int64_t ld, int tile, int S, int fr, int g, bf16x8 (&q)[2]) {
+  const int qrow = min(tile * 16 + fr, S - 1);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) q[s] = *(const bf16x8*)(qb + (int64_t)qrow * ld + 32 * s + 8 * g);
+}
+
+// ds_read_b64_tr_b16 of the row-major V image, and the V^T A-operand fragment of two of them (the
+// second `hi` bytes further on: the next 4-key group of the MFMA's k order)
+__device__ __forceinline__ s16x4 tr_read(const char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(LDS_AS char*)(uintptr_t)(const LDS_AS char*)p);
+}
+__device__ __forceinline__ bf16x8 vfrag(const char* p, int hi) {
+  const s16x4 lo = tr_read(p);
+  const s16x4 up = tr_read(p + hi);
+  return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// Where a (sequence, head)'s output rows go, and in which format: bf16 rows of `out`, or (q8) MX-fp8
+// rows of q8 with the head's 64 dims as one 64-k block of out_proj, scale bytes in qs.  The
+// accumulators are normalised by inv = 1 / l on the way out.  Built at the call, AttnOut{...}.store16(...):
+// kept in a variable that the kernels' lambdas capture by reference, it changed the product kernels'
+// code (profiles/attention_isa.log).
+struct AttnOut {
+  uint16_t* out;
+  uint8_t* q8;
+  uint8_t* qs;
+  int64_t rows_pad;
+  int bseq, S, W, h;
+
+  // 16x16 C layout, o[dt][j]: query qrow, head dim dt*16 + 4g + j.  bf16 of one row qrow < S:
+  __device__ __forceinline__ void row16_bf16(int qrow, int g, const f32x4 (&o)[4], float inv) const {
+    uint16_t* dst = out + ((int64_t)bseq * S + qrow) * W + h * 64 + 4 * g;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+      *(uint2*)(dst + dt * 16) = make_uint2(pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv),
+                                            pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv));
+  }
+  // ... in either format, rows >= S dropped (every lane of the wave calls this: the MX block's amax is
+  // reduced across the row's four lanes)
+  __device__ __forceinline__ void store16(int qrow, int g, const f32x4 (&o)[4], float inv) const {
+    if (q8) {
+      float amax = 0.f;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(o[dt][j] * inv));
+      amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+      amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+      const int X = mx_block_exp(amax);
+      const float scl = ldexpf(1.0f, -X);
+      if (qrow < S) {
+        const int64_t row = (int64_t)bseq * S + qrow;
+        uint8_t* dst = q8 + row * W + h * 64 + 4 * g;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+          *(uint32_t*)(dst + dt * 16) = mx_pack4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv, scl);
+        if (g == 0) qs[mx_scale_index(row, h, rows_pad)] = (uint8_t)(X + 127);
+      }
+      return;
+    }
+    if (qrow < S) row16_bf16(qrow, g, o, inv);
+  }
+};
+
 // --------------------------------------------------------------- attention
 // One wave per (sequence, head), head dim 64, whole padded sequence (SP rows,
 // multiple of 32) per wave; no workgroup barriers.
@@ -171,10 +287,10 @@ __device__ __forceinline__ void attention_flash_body(const uint16_t* __restrict_
                                                      int S, int W, int H, int causal, uint8_t* __restrict__ q8,
                                                      uint8_t* __restrict__ qs, int64_t rows_pad, int items = 0) {
   static_assert(!PIPE || (NT == 1 && SLOTS == 1 && HP == 1), "PIPE: the single-chunk instance only");
-  // causal bit 11: the first 16-query tile only (the last vision block, whose outputs are read at the
+  // ATT_Q0_ONLY: the first 16-query tile only (the last vision block, whose outputs are read at the
   // CLS rows alone, api.cpp last_block_cls); the other tiles' waves still stage K / V
-  const bool q0only = (causal >> 11) & 1;
-  causal &= 1;
+  const bool q0only = causal & ATT_Q0_ONLY;
+  causal &= ATT_CAUSAL;
   constexpr int KS = 72, VS = 68;  // LDS row strides (bf16)
   const int NW = PP == 1 ? 8 : (int)(blockDim.x >> 6) / HP;  // PP = 1 is launched with 8 waves
   __shared__ __attribute__((aligned(16))) uint16_t Ksh[HP][SLOTS][64 * KS];
@@ -184,29 +300,20 @@ __device__ __forceinline__ void attention_flash_body(const uint16_t* __restrict_
   uint16_t(*Vs)[64 * VS] = Vsh[hh];
   const int tid = threadIdx.x - hh * 64 * NW, lane = tid & 63, wave = tid >> 6;
   const int64_t ld = 3 * (int64_t)W;
-  int item = blockIdx.x;
-  bool first = true;
-  uint4 kr_n[PP], vr_n[PP];   // PIPE: the next item's K / V pieces and Q fragments
-  bf16x8 qf_n[2];
-  for (;;) {
-  const int bseq = item / (H / HP), h = (item % (H / HP)) * HP + hh;
-  const uint16_t* qb = qkv + (int64_t)bseq * S * ld + h * 64;
-  const uint16_t* kb = qb + W;
-  const uint16_t* vb = qb + 2 * W;
-  const int nch = (S + 63) / 64, nqt = q0only ? 1 : (S + 15) / 16;
-  const int fr = lane & 15, g = lane >> 4, fk = 8 * g;
-  const float sl2 = 0.125f * 1.4426950408889634f;  // head_dim^-0.5 * log2(e)
-  constexpr float RESCALE = 8.0f;                  // lazy-rescale threshold (log2 units)
-
-  uint4 kr[PP], vr[PP];
-#define FA_STAGE_LOAD(c)                                                                  \
+  // Staging of one 64-key chunk, in two halves around the previous chunk's math.  First half: this
+  // thread's PP 16-byte pieces of K and of V (rows c*64.. of an item's kb_ / vb_; rows >= S: zeros) into
+  // the registers kr_ / vr_; second half: the pieces into a ring slot, K row-major, V transposed.
+  // These two stay macros, the only ones in the file: as lambdas or as functions, however their
+  // operands were passed, every product instantiation of this kernel compiled to other code
+  // (profiles/attention_isa.log).
+#define FA_STAGE_LOAD(kb_, vb_, c, kr_, vr_)                                              \
   _Pragma("unroll") for (int i = 0; i < PP; ++i) {                                        \
     const int p_ = tid + i * 64 * NW, r_ = (c) * 64 + (p_ >> 3), ch_ = p_ & 7;            \
-    kr[i] = make_uint4(0, 0, 0, 0);                                                       \
-    vr[i] = make_uint4(0, 0, 0, 0);                                                       \
+    kr_[i] = make_uint4(0, 0, 0, 0);                                                      \
+    vr_[i] = make_uint4(0, 0, 0, 0);                                                      \
     if ((PP == 1 || p_ < 512) && r_ < S) {                                                \
-      kr[i] = *(const uint4*)(kb + (int64_t)r_ * ld + ch_ * 8);                           \
-      vr[i] = *(const uint4*)(vb + (int64_t)r_ * ld + ch_ * 8);                           \
+      kr_[i] = *(const uint4*)((kb_) + (int64_t)r_ * ld + ch_ * 8);                       \
+      vr_[i] = *(const uint4*)((vb_) + (int64_t)r_ * ld + ch_ * 8);                       \
     }                                                                                     \
   }
 #define FA_STAGE_WRITE(slot)                                                              \
@@ -218,12 +325,26 @@ __device__ __forceinline__ void attention_flash_body(const uint16_t* __restrict_
       _Pragma("unroll") for (int e = 0; e < 8; ++e) Vs[slot][(ch_ * 8 + e) * VS + r_] = vv_[e]; \
     }                                                                                     \
   }
+  int item = blockIdx.x;
+  bool first = true;
+  uint4 kr_n[PP], vr_n[PP];   // PIPE: the next item's K / V pieces and Q fragments
+  bf16x8 qf_n[2];
+  for (;;) {
+  const int bseq = item / (H / HP), h = (item % (H / HP)) * HP + hh;
+  const uint16_t* qb = qkv + (int64_t)bseq * S * ld + h * 64;
+  const uint16_t* kb = qb + W;
+  const uint16_t* vb = qb + 2 * W;
+  const int nch = (S + 63) / 64, nqt = q0only ? 1 : (S + 15) / 16;
+  const int fr = lane & 15, g = lane >> 4, fk = 8 * g;
 
+  uint4 kr[PP], vr[PP];
   bf16x8 qf[NT][2];
   float m[NT], l[NT];
   f32x4 o[NT][4];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
+    // (load_q16 and, below, lazy_rescale written out: through the helpers the single-tile product
+    // kernels <1, 1> and <1, 2, 1> compiled to other code, profiles/attention_isa.log)
     const int qrow = min((wave + NW * t) * 16 + fr, S - 1);
 #pragma unroll
     for (int s = 0; s < 2; ++s) qf[t][s] = (!PIPE || first) ? *(const bf16x8*)(qb + (int64_t)qrow * ld + 32 * s + fk) : qf_n[s];
@@ -233,7 +354,7 @@ __device__ __forceinline__ void attention_flash_body(const uint16_t* __restrict_
     for (int dt = 0; dt < 4; ++dt) o[t][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   if (!PIPE || first) {
-    FA_STAGE_LOAD(0);
+    FA_STAGE_LOAD(kb, vb, 0, kr, vr);
   } else {
 #pragma unroll
     for (int i = 0; i < PP; ++i) {
@@ -247,24 +368,13 @@ __device__ __forceinline__ void attention_flash_body(const uint16_t* __restrict_
   if (PIPE && item + (int)gridDim.x < items) {   // the next item's operands, in flight during this one
     const int nx = item + (int)gridDim.x;
     const uint16_t* nq = qkv + (int64_t)(nx / H) * S * ld + (nx % H) * 64;
-    const int qrow = min(wave * 16 + fr, S - 1);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) qf_n[s] = *(const bf16x8*)(nq + (int64_t)qrow * ld + 32 * s + fk);
-#pragma unroll
-    for (int i = 0; i < PP; ++i) {
-      const int p_ = tid + i * 64 * NW, r_ = p_ >> 3, ch_ = p_ & 7;
-      kr_n[i] = make_uint4(0, 0, 0, 0);
-      vr_n[i] = make_uint4(0, 0, 0, 0);
-      if ((PP == 1 || p_ < 512) && r_ < S) {
-        kr_n[i] = *(const uint4*)(nq + W + (int64_t)r_ * ld + ch_ * 8);
-        vr_n[i] = *(const uint4*)(nq + 2 * W + (int64_t)r_ * ld + ch_ * 8);
-      }
-    }
+    load_q16(nq, ld, wave, S, fr, g, qf_n);
+    FA_STAGE_LOAD(nq + W, nq + 2 * W, 0, kr_n, vr_n);
   }
 
   for (int c = 0; c < nch; ++c) {
     const int slot = SLOTS == 1 ? 0 : (c & 1);
-    if (SLOTS > 1 && c + 1 < nch) FA_STAGE_LOAD(c + 1);
+    if (SLOTS > 1 && c + 1 < nch) FA_STAGE_LOAD(kb, vb, c + 1, kr, vr);
     const int kvalid = min(64, S - c * 64);  // keys of this chunk < S
     bf16x8 kf[4][2], vf[4][2];
 #pragma unroll
@@ -315,12 +425,7 @@ __device__ __forceinline__ void attention_flash_body(const uint16_t* __restrict_
                        fmaxf(fmaxf(sc[1][0], sc[1][1]), fmaxf(sc[1][2], sc[1][3])));
       cm = fmaxf(cm, fmaxf(fmaxf(fmaxf(sc[2][0], sc[2][1]), fmaxf(sc[2][2], sc[2][3])),
                            fmaxf(fmaxf(sc[3][0], sc[3][1]), fmaxf(sc[3][2], sc[3][3]))));
-      {
-        const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(cm), __float_as_uint(cm), false, false);
-        cm = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-        const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(cm), __float_as_uint(cm), false, false);
-        cm = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-      }
+      cm = group_max(cm);
       const float cmu = cm * sl2;  // finite: chunk 0 holds key 0 <= every row
       if (cmu > m[t] + RESCALE) {
         const float alpha = __builtin_amdgcn_exp2f(m[t] - cmu);
@@ -366,44 +471,7 @@ __device__ __forceinline__ void attention_flash_body(const uint16_t* __restrict_
   for (int t = 0; t < NT; ++t) {
     const int qt = wave + NW * t;
     if (qt >= nqt) continue;
-    const int qrow = qt * 16 + fr;
-    float lt = l[t];
-    {
-      const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(lt), __float_as_uint(lt), false, false);
-      lt = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-      const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(lt), __float_as_uint(lt), false, false);
-      lt = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-    }
-    const float inv = 1.0f / lt;
-    // o[t][dt][j]: query qrow, head dim dt*16 + 4g + j
-    if (q8) {  // MX-fp8 output: this head's 64 dims are one 64-k block of out_proj
-      float amax = 0.f;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(o[t][dt][j] * inv));
-      amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-      amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-      const int X = mx_block_exp(amax);
-      const float scl = ldexpf(1.0f, -X);
-      if (qrow < S) {
-        const int64_t row = (int64_t)bseq * S + qrow;
-        uint8_t* dst = q8 + row * W + h * 64 + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-          *(uint32_t*)(dst + dt * 16) =
-              mx_pack4(o[t][dt][0] * inv, o[t][dt][1] * inv, o[t][dt][2] * inv, o[t][dt][3] * inv, scl);
-        if (g == 0) qs[mx_scale_index(row, h, rows_pad)] = (uint8_t)(X + 127);
-      }
-      continue;
-    }
-    if (qrow < S) {
-      uint16_t* dst = out + ((int64_t)bseq * S + qrow) * W + h * 64 + 4 * g;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-        *(uint2*)(dst + dt * 16) = make_uint2(pack_bf16x2(o[t][dt][0] * inv, o[t][dt][1] * inv),
-                                              pack_bf16x2(o[t][dt][2] * inv, o[t][dt][3] * inv));
-    }
+    AttnOut{out, q8, qs, rows_pad, bseq, S, W, h}.store16(qt * 16 + fr, g, o[t], 1.0f / group_sum(l[t]));
   }
   if (!PIPE) break;
   item += (int)gridDim.x;
@@ -492,7 +560,9 @@ __global__ __launch_bounds__(NW * 64) void attention_res_kernel(const uint16_t* 
   const uint16_t* kb = qb + W;
   const uint16_t* vb = qb + 2 * W;
 
-  // ---- K, V -> LDS (one DMA instruction = 8 rows)
+  // ---- K, V -> LDS (one DMA instruction = 8 rows).  This loop and attention_r32_kernel's differ only
+  // in the V swizzle term, and both stay written out: as one shared function either product kernel
+  // came out with its loop's address arithmetic compiled differently (profiles/attention_isa.log).
   {
     const int nr8 = spad >> 3;
     const int slot = lane & 7;
@@ -508,27 +578,16 @@ __global__ __launch_bounds__(NW * 64) void attention_res_kernel(const uint16_t* 
   const int nqt = (S + 15) / 16, nch = (S + 63) / 64;
   const int last_kvalid = S - (nch - 1) * 64;   // 1..64
   const int fr = lane & 15, g = lane >> 4;
-  const float sl2 = 0.125f * 1.4426950408889634f;  // head_dim^-0.5 * log2(e)
-  constexpr float RESCALE = 8.0f;
   const int rk0 = fr * 128 + (((0 + g) ^ (fr >> 1)) << 4);
   const int rk1 = fr * 128 + (((4 + g) ^ (fr >> 1)) << 4);
   const int vq = (lane & 15) >> 2, vp = lane & 3;
   const int vx = (2 * g + (vq >> 1)) & 3;
   const int rvb = (4 * g + vq) * 128 + vp * 8;
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  auto tr_read = [&](const char* p) -> s16x4 {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(LDS_AS char*)(uintptr_t)(const LDS_AS char*)p);
-  };
 
   // QPF (A/B): a tile's Q fragments are loaded one tile ahead (the wave's first tile's beside the
   // K/V load), so their latency is not exposed at the head of every tile
   bf16x8 qn[2];
-  auto load_q = [&](int t, bf16x8 (&q)[2]) {
-    const int qrow = min(t * 16 + fr, S - 1);
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) q[s2] = *(const bf16x8*)(qb + (int64_t)qrow * ld + 32 * s2 + 8 * g);
-  };
-  if (QPF) load_q(wave, qn);
+  if (QPF) load_q16(qb, ld, wave, S, fr, g, qn);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -544,14 +603,10 @@ __global__ __launch_bounds__(NW * 64) void attention_res_kernel(const uint16_t* 
     if (QPF && TT == 1) {
       qf[0][0] = qn[0];
       qf[0][1] = qn[1];
-      if (t0 + NW < (SPLIT ? nqt - 1 : nqt)) load_q(t0 + NW, qn);   // the wave's next tile
+      if (t0 + NW < (SPLIT ? nqt - 1 : nqt)) load_q16(qb, ld, t0 + NW, S, fr, g, qn);   // the wave's next tile
     } else {
 #pragma unroll
-      for (int u = 0; u < TT; ++u) {
-        const int qrow = min(tq[u] * 16 + fr, S - 1);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) qf[u][s2] = *(const bf16x8*)(qb + (int64_t)qrow * ld + 32 * s2 + 8 * g);
-      }
+      for (int u = 0; u < TT; ++u) load_q16(qb, ld, tq[u], S, fr, g, qf[u]);
     }
     float m[TT], l[TT];
     f32x4 o[TT][4];
@@ -593,20 +648,9 @@ __global__ __launch_bounds__(NW * 64) void attention_res_kernel(const uint16_t* 
 #pragma unroll
         for (int kt = 1; kt < NKT; ++kt)
           cm = fmaxf(cm, fmaxf(fmaxf(sc[u][kt][0], sc[u][kt][1]), fmaxf(sc[u][kt][2], sc[u][kt][3])));
-        {
-          const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(cm), __float_as_uint(cm), false, false);
-          cm = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-          const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(cm), __float_as_uint(cm), false, false);
-          cm = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-        }
+        cm = group_max(cm);
         const float cmu = cm * sl2;   // finite: chunk 0 holds key 0 for every row
-        if (cmu > m[u] + RESCALE) {
-          const float alpha = __builtin_amdgcn_exp2f(m[u] - cmu);
-          l[u] *= alpha;
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) o[u][dt] *= alpha;
-          m[u] = cmu;
-        }
+        lazy_rescale(m[u], l[u], o[u], cmu);
         float ps = 0.f;
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
@@ -629,72 +673,24 @@ __global__ __launch_bounds__(NW * 64) void attention_res_kernel(const uint16_t* 
         const char* vc = Vimg + (c * 64 + 32 * s2) * 128 + rvb;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          const s16x4 lo = tr_read(vc + ((dt ^ vx) << 5));
-          const s16x4 hi = tr_read(vc + 16 * 128 + ((dt ^ vx) << 5));
-          typedef short s16x8 __attribute__((ext_vector_type(8)));
-          const s16x8 v8 = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-          const bf16x8 vf = __builtin_bit_cast(bf16x8, v8);
+          const bf16x8 vf = vfrag(vc + ((dt ^ vx) << 5), 16 * 128);
 #pragma unroll
           for (int u = 0; u < TT; ++u) o[u][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[u], o[u][dt], 0, 0, 0);
         }
       }
     };
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    using I4 = std::integral_constant<int, 4>;
-    using BF = std::integral_constant<bool, false>;
-    using BT = std::integral_constant<bool, true>;
-    for (int c = 0; c < nch - 1; ++c) chunk(I4{}, BF{}, c);
+    for (int c = 0; c < nch - 1; ++c) chunk(Int<4>{}, std::bool_constant<false>{}, c);
     {
       const int c = nch - 1;
-      if (last_kvalid > 48) chunk(I4{}, BT{}, c);
-      else if (last_kvalid > 32) chunk(I3{}, BT{}, c);
-      else if (last_kvalid > 16) chunk(I2{}, BT{}, c);
-      else chunk(I1{}, BT{}, c);
+      if (last_kvalid > 48) chunk(Int<4>{}, std::bool_constant<true>{}, c);
+      else if (last_kvalid > 32) chunk(Int<3>{}, std::bool_constant<true>{}, c);
+      else if (last_kvalid > 16) chunk(Int<2>{}, std::bool_constant<true>{}, c);
+      else chunk(Int<1>{}, std::bool_constant<true>{}, c);
     }
 
 #pragma unroll
-    for (int u = 0; u < TT; ++u) {
-      float lt = l[u];
-      {
-        const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(lt), __float_as_uint(lt), false, false);
-        lt = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-        const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(lt), __float_as_uint(lt), false, false);
-        lt = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-      }
-      const float inv = 1.0f / lt;
-      const int qrow = tq[u] * 16 + fr;
-      // o[u][dt][j]: query qrow, head dim dt*16 + 4g + j
-      if (q8) {  // MX-fp8 output: this head's 64 dims are one 64-k block of out_proj
-        float amax = 0.f;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(o[u][dt][j] * inv));
-        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        const int X = mx_block_exp(amax);
-        const float scl = ldexpf(1.0f, -X);
-        if (qrow < S) {
-          const int64_t row = (int64_t)bseq * S + qrow;
-          uint8_t* dst = q8 + row * W + h * 64 + 4 * g;
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt)
-            *(uint32_t*)(dst + dt * 16) =
-                mx_pack4(o[u][dt][0] * inv, o[u][dt][1] * inv, o[u][dt][2] * inv, o[u][dt][3] * inv, scl);
-          if (g == 0) qs[mx_scale_index(row, h, rows_pad)] = (uint8_t)(X + 127);
-        }
-        continue;
-      }
-      if (qrow < S) {
-        uint16_t* dst = out + ((int64_t)bseq * S + qrow) * W + h * 64 + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-          *(uint2*)(dst + dt * 16) = make_uint2(pack_bf16x2(o[u][dt][0] * inv, o[u][dt][1] * inv),
-                                                pack_bf16x2(o[u][dt][2] * inv, o[u][dt][3] * inv));
-      }
-    }
+    for (int u = 0; u < TT; ++u)
+      AttnOut{out, q8, qs, rows_pad, bseq, S, W, h}.store16(tq[u] * 16 + fr, g, o[u], 1.0f / group_sum(l[u]));
   };
   // SPLIT: the last tile's rows over this wave's key tiles, partial states to LDS (SFIRST: before the
   // full tiles, so every wave reaches the merge barrier with the same work behind it)
@@ -704,11 +700,7 @@ __global__ __launch_bounds__(NW * 64) void attention_res_kernel(const uint16_t* 
     const int tl = nqt - 1, vr = S - 16 * tl;
     const int nkt = (S + 15) / 16;
     bf16x8 qf[2];
-    {
-      const int qrow = min(tl * 16 + fr, S - 1);
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) qf[s2] = *(const bf16x8*)(qb + (int64_t)qrow * ld + 32 * s2 + 8 * g);
-    }
+    load_q16(qb, ld, tl, S, fr, g, qf);
     float m = -INFINITY, l = 0.f;
     f32x4 o[4];
 #pragma unroll
@@ -722,21 +714,9 @@ __global__ __launch_bounds__(NW * 64) void attention_res_kernel(const uint16_t* 
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (kb + 4 * g + j >= S) sc[j] = -INFINITY;
-      float cm = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
-      {
-        const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(cm), __float_as_uint(cm), false, false);
-        cm = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-        const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(cm), __float_as_uint(cm), false, false);
-        cm = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-      }
+      const float cm = group_max(fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3])));
       const float cmu = cm * sl2;   // finite: key tile kb < S holds key kb
-      if (cmu > m + RESCALE) {
-        const float alpha = __builtin_amdgcn_exp2f(m - cmu);
-        l *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
-        m = cmu;
-      }
+      lazy_rescale(m, l, o, cmu);
 #pragma unroll
       for (int j = 0; j < 4; ++j) sc[j] = __builtin_amdgcn_exp2f(fmaf(sc[j], sl2, -m));
       l += (sc[0] + sc[1]) + (sc[2] + sc[3]);
@@ -748,21 +728,10 @@ __global__ __launch_bounds__(NW * 64) void attention_res_kernel(const uint16_t* 
       }
       const char* vc = Vimg + kb * 128 + rvb;
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const s16x4 lo = tr_read(vc + ((dt ^ vx) << 5));
-        const s16x4 hi = tr_read(vc + 16 * 128 + ((dt ^ vx) << 5));
-        typedef short s16x8 __attribute__((ext_vector_type(8)));
-        const s16x8 v8 = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, v8), pb, o[dt], 0, 0, 0);
-      }
+      for (int dt = 0; dt < 4; ++dt)
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfrag(vc + ((dt ^ vx) << 5), 16 * 128), pb, o[dt], 0, 0, 0);
     }
-    float lt = l;
-    {
-      const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(lt), __float_as_uint(lt), false, false);
-      lt = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-      const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(lt), __float_as_uint(lt), false, false);
-      lt = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-    }
+    const float lt = group_sum(l);
     // partial states of the valid rows: [wave][row][m, l, o 0..63] after the K / V images
     float* part = (float*)(res_lds + 2 * spad * 128);
     if (fr < vr) {
@@ -780,14 +749,14 @@ __global__ __launch_bounds__(NW * 64) void attention_res_kernel(const uint16_t* 
   if (SPLIT && SFIRST) split_part();
   const int nfull = SPLIT ? nqt - 1 : nqt;   // SPLIT: the last tile is shared out below
   for (int t = wave; t < nfull; t += 2 * NW) {
-    if (TT2 && t + NW < nfull) tiles(std::integral_constant<int, 2>{}, t, t + NW);
+    if (TT2 && t + NW < nfull) tiles(Int<2>{}, t, t + NW);
     else {
-      tiles(std::integral_constant<int, 1>{}, t, t);
-      if (!TT2 && t + NW < nfull) tiles(std::integral_constant<int, 1>{}, t + NW, t + NW);
+      tiles(Int<1>{}, t, t);
+      if (!TT2 && t + NW < nfull) tiles(Int<1>{}, t + NW, t + NW);
     }
   }
   if (SPLIT && !SFIRST) split_part();
-  if (SPLIT) {
+  if (SPLIT) {   // (launched with bf16 output only: attention() runs the unsplit kernel when q8 is set)
     const int tl = nqt - 1, vr = S - 16 * tl;
     float* part = (float*)(res_lds + 2 * spad * 128);
     __syncthreads();
@@ -809,16 +778,7 @@ __global__ __launch_bounds__(NW * 64) void attention_res_kernel(const uint16_t* 
 #pragma unroll
           for (int j = 0; j < 4; ++j) O[dt][j] += pw[4 + dt * 16 + 4 * g + j] * sw;
       }
-      const float inv = 1.0f / L;
-      const int qrow = tl * 16 + fr;
-      if (q8) {   // never taken: the MX tower's attention runs the 32x32 kernel (SPLIT is bf16 only)
-      } else {
-        uint16_t* dst = out + ((int64_t)bseq * S + qrow) * W + h * 64 + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-          *(uint2*)(dst + dt * 16) = make_uint2(pack_bf16x2(O[dt][0] * inv, O[dt][1] * inv),
-                                                pack_bf16x2(O[dt][2] * inv, O[dt][3] * inv));
-      }
+      AttnOut{out, q8, qs, rows_pad, bseq, S, W, h}.row16_bf16(tl * 16 + fr, g, O, 1.0f / L);   // (fr < vr: a row < S)
     }
   }
 }
@@ -945,20 +905,8 @@ __global__ __launch_bounds__(NW * 64) void attention_r32_kernel(const uint16_t* 
   const int vrow = (4 * hh + tq) * 128 + 8 * (tp & 1);
   const int vof0 = vrow + 16 * ((0 + 2 * gq + (tp >> 1)) ^ ((tq >> 1) << 2));
   const int vof1 = vrow + 16 * ((4 + 2 * gq + (tp >> 1)) ^ ((tq >> 1) << 2));
-  const float sl2 = 0.125f * 1.4426950408889634f;   // head_dim^-0.5 * log2(e)
-  constexpr float RESCALE = 8.0f;
   const int nqb = (S + 31) >> 5;
   const int last_keys = S - (nch - 1) * 64;   // 1..64
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  auto tr_read = [&](const char* p) -> s16x4 {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(LDS_AS char*)(uintptr_t)(const LDS_AS char*)p);
-  };
-  auto vfrag = [&](const char* p) -> bf16x8 {
-    const s16x4 lo = tr_read(p);
-    const s16x4 hi = tr_read(p + 8 * 128);
-    return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-  };
 
   if (PH2) {   // this wave's first-phase DMAs (and Q): the NI2 - n0 younger ones may stay in flight
     const int n0 = 2 * h0 > wave ? (2 * h0 - wave + NW - 1) / NW : 0;
@@ -1022,18 +970,9 @@ __global__ __launch_bounds__(NW * 64) void attention_r32_kernel(const uint16_t* 
         for (int kt = 0; kt < NKB; ++kt)
 #pragma unroll
           for (int i = (kt ? 0 : 1); i < 16; ++i) cm = fmaxf(cm, x[u][kt][i]);
-        {
-          const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(cm), __float_as_uint(cm), false, false);
-          cm = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-        }
+        cm = group_max<false>(cm);
         const float cmu = cm * sl2;   // finite: chunk 0 holds key 0 for every row
-        if (cmu > m[u] + RESCALE) {
-          const float alpha = __builtin_amdgcn_exp2f(m[u] - cmu);
-          l[u] *= alpha;
-          o[u][0] *= alpha;
-          o[u][1] *= alpha;
-          m[u] = cmu;
-        }
+        lazy_rescale(m[u], l[u], o[u], cmu);
         float ps = 0.f;
 #pragma unroll
         for (int kt = 0; kt < NKB; ++kt) {
@@ -1050,8 +989,8 @@ __global__ __launch_bounds__(NW * 64) void attention_r32_kernel(const uint16_t* 
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           const char* vp = Vimg + (c * 64 + kt * 32 + 16 * s) * 128;
-          const bf16x8 v0 = vfrag(vp + vof0);
-          const bf16x8 v1 = vfrag(vp + vof1);
+          const bf16x8 v0 = vfrag(vp + vof0, 8 * 128);
+          const bf16x8 v1 = vfrag(vp + vof1, 8 * 128);
 #pragma unroll
           for (int u = 0; u < TT; ++u) {
             uint32_t pk[4];
@@ -1064,32 +1003,26 @@ __global__ __launch_bounds__(NW * 64) void attention_r32_kernel(const uint16_t* 
           }
         }
     };
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using BF = std::integral_constant<bool, false>;
-    using BT = std::integral_constant<bool, true>;
     for (int c = 0; c < nch - 1; ++c) {
       if (PH2 && first && c == c0) {   // the second load phase (every wave passes here once)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
       }
-      chunk(I2{}, BF{}, c);
+      chunk(Int<2>{}, std::bool_constant<false>{}, c);
     }
     if (PH2 && first && c0 >= nch - 1) {   // short sequences: the second phase before the last chunk
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
     }
-    if (last_keys > 32) chunk(I2{}, BT{}, nch - 1);
-    else chunk(I1{}, BT{}, nch - 1);
+    if (last_keys > 32) chunk(Int<2>{}, std::bool_constant<true>{}, nch - 1);
+    else chunk(Int<1>{}, std::bool_constant<true>{}, nch - 1);
 
+    // The epilogue of the 32x32 layout has this one site and stays written out: as a member of
+    // AttnOut beside store16 it moved instructions in the product kernel's K/V load loop
+    // (profiles/attention_isa.log).
 #pragma unroll
     for (int u = 0; u < TT; ++u) {
-      float lt = l[u];
-      {
-        const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(lt), __float_as_uint(lt), false, false);
-        lt = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-      }
-      const float inv = 1.0f / lt;
+      const float inv = 1.0f / group_sum<false>(l[u]);
       const int qrow = bq[u] * 32 + r;
       // o[u][db][i]: query qrow, head dim 32 db + (i & 3) + 8 (i >> 2) + 4 hh
       if (q8) {   // MX-fp8 output: this head's 64 dims are one 64-k block of out_proj
@@ -1098,10 +1031,7 @@ __global__ __launch_bounds__(NW * 64) void attention_r32_kernel(const uint16_t* 
         for (int db = 0; db < 2; ++db)
 #pragma unroll
           for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(o[u][db][i] * inv));
-        {
-          const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(amax), __float_as_uint(amax), false, false);
-          amax = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-        }
+        amax = group_max<false>(amax);
         const int X = mx_block_exp(amax);
         const float scl = ldexpf(1.0f, -X);
         if (qrow < S) {
@@ -1130,181 +1060,144 @@ __global__ __launch_bounds__(NW * 64) void attention_r32_kernel(const uint16_t* 
   };
   if (TT2) {
     for (int b = wave; b < nqb; b += 2 * NW) {
-      if (b + NW < nqb) blocks(std::integral_constant<int, 2>{}, b, b + NW, false);
-      else blocks(std::integral_constant<int, 1>{}, b, b, false);
+      if (b + NW < nqb) blocks(Int<2>{}, b, b + NW, false);
+      else blocks(Int<1>{}, b, b, false);
     }
   } else {
     if (PH2 && wave >= nqb) {   // no block: the second phase's barrier all the same
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
     }
-    for (int b = wave; b < nqb; b += NW) blocks(std::integral_constant<int, 1>{}, b, b, b == wave);
+    for (int b = wave; b < nqb; b += NW) blocks(Int<1>{}, b, b, b == wave);
   }
 }
 
 }  // namespace
 
-hipError_t attention(const uint16_t* qkv, uint16_t* out, int B, int S, int W, int causal, hipStream_t s, uint8_t* q8,
+// A compile-time kernel pointer handed to a generic lambda (launch_kernel<K::value>)
+template <auto KERNEL>
+using Kern = std::integral_constant<decltype(KERNEL), KERNEL>;
+
+hipError_t attention(const uint16_t* qkv, uint16_t* out, int B, int S, int W, int flags, hipStream_t s, uint8_t* q8,
                      uint8_t* qs) {
   const int H = W / 64;
   const int items = B * H;
   if (items <= 0) return hipSuccess;
   if (S > 640) return hipErrorInvalidValue;
-  // Every length runs attention_flash_kernel (scripts/attn_micro.py, this
+  // Every length has a flash kernel (scripts/attn_micro.py, this
   // round: B/32 S=50 177 vs 181 us for the one-wave kernel, text S=77 25.9 vs
   // 30.0, L/14 408 vs 572 and L/14@336 547 vs 1004 for the per-query-tile-K
-  // kernel it replaced).  Causal bit 8 selects the one-wave kernel for S <= 96
+  // kernel it replaced).  ATT_ONE_WAVE selects the one-wave kernel for S <= 96
   // (A/B and parity tests of both paths; it has no fp8 output).
+
+  // ---- 1. flags (AttnFlags, internal.hpp)
 #if MICLIP_AB
-  const bool one_wave = ((causal >> 8) & 1) && S <= 96 && !q8;
+  const bool one_wave = (flags & ATT_ONE_WAVE) && S <= 96 && !q8;
 #else
-  if ((causal >> 8) & 1) return hipErrorNotSupported;   // the one-wave kernel is in the A/B build only
+  if (flags & ATT_ONE_WAVE) return hipErrorNotSupported;   // the one-wave kernel is in the A/B build only
   constexpr bool one_wave = false;
 #endif
-  const bool old_flash = (causal >> 9) & 1;   // A/B: the chunk-streaming flash kernel for S > 64
-  const int q0only = (causal >> 11) & 1;      // the first query tile only (S <= 64 kernel; others compute all)
-  causal &= 1;
-  const dim3 grid(items);
+  const bool stream = flags & ATT_STREAM;   // A/B: the chunk-streaming flash kernel for S > 64
+  const int q0 = flags & ATT_Q0_ONLY;       // the first query tile only (S <= 64 kernel; others compute all)
+  const int causal = flags & ATT_CAUSAL;
+  const int64_t rows_pad = ((int64_t)B * S + 1) & ~1;   // rows of the MX scale layout (mx_scale_index)
+  const size_t res_lds = 2 * (size_t)((S + 31) & ~31) * 128;   // resident kernels: the K and V images
+
+  // ---- 2. A/B only: MICLIP_ATTN_SHORT, the S <= 64 variants (described at their kernels)
 #if MICLIP_AB
-  // A/B: MICLIP_ATTN_SHORT=1 runs S <= 64 (non-causal) on the resident-K/V kernel with 4 waves
-  const char* se = std::getenv("MICLIP_ATTN_SHORT");
-  // 5x: persistent workgroups with the next item's operands prefetched, x workgroups per CU (default 4:
-  // 128 VGPRs)
-  if (se && se[0] == '5' && !one_wave && !old_flash && S <= 64) {
-    const int per = se[1] ? std::atoi(se + 1) : 4;
-    const int gp = std::min(items, cu_count() * (per > 0 ? per : 5));
-    hipLaunchKernelGGL(attention_pipe_kernel, dim3(gp), dim3(256), 0, s, qkv, out, S, W, H, causal, q8, qs,
-                       ((int64_t)B * S + 1) & ~1, items);
-    return hipGetLastError();
-  }
-  // 6: the V^T fragment reads batched (attention_vb_kernel)
-  if (se && se[0] == '6' && !one_wave && !old_flash && S <= 64) {
-    hipLaunchKernelGGL(attention_vb_kernel, grid, dim3(256), 0, s, qkv, out, S, W, H, causal | (q0only << 11), q8, qs,
-                       ((int64_t)B * S + 1) & ~1);
-    return hipGetLastError();
-  }
-  // 2: two heads per workgroup; 3: the occupancy-targeted single-head kernel
-  if (se && (se[0] == '2' || se[0] == '3') && !one_wave && !old_flash && S <= 64) {
-    if (se[0] == '2' && H % 2 == 0)
-      hipLaunchKernelGGL(attention_short2_kernel, dim3(items / 2), dim3(512), 0, s, qkv, out, S, W, H, causal, q8, qs,
-                         ((int64_t)B * S + 1) & ~1);
-    else
-      hipLaunchKernelGGL(attention_short_kernel, grid, dim3(256), 0, s, qkv, out, S, W, H, causal, q8, qs,
-                         ((int64_t)B * S + 1) & ~1);
-    return hipGetLastError();
-  }
-  if (se && se[0] == '1' && !one_wave && !old_flash && !(causal & 1) && S <= 64) {
-    const size_t lds = 2 * (size_t)((S + 31) & ~31) * 128;
-    hipLaunchKernelGGL((attention_res_kernel<4, false>), dim3(B * (W / 64)), dim3(256), lds, s, qkv, out, S, W, W / 64,
-                       q8, qs, ((int64_t)B * S + 1) & ~1);
-    return hipGetLastError();
+  if (!one_wave && !stream && S <= 64) {
+    const int sw = ab_env_int("MICLIP_ATTN_SHORT", 0);
+    // 5x: persistent workgroups with the next item's operands prefetched, x workgroups per CU (a bare 5: 4 per
+    // CU: 128 VGPRs)
+    if (sw == 5 || sw / 10 == 5) {
+      const int per = sw == 5 ? 4 : sw % 10;
+      const int gp = std::min(items, cu_count() * (per > 0 ? per : 5));
+      return launch_kernel(attention_pipe_kernel, gp, 256, s, qkv, out, S, W, H, causal, q8, qs, rows_pad, items);
+    }
+    switch (sw) {
+      case 6:   // the V^T fragment reads batched
+        return launch_kernel(attention_vb_kernel, items, 256, s, qkv, out, S, W, H, causal | q0, q8, qs, rows_pad);
+      case 2:   // two heads per workgroup (an odd H: as 3)
+        if (H % 2 == 0)
+          return launch_kernel(attention_short2_kernel, items / 2, 512, s, qkv, out, S, W, H, causal, q8, qs, rows_pad);
+        [[fallthrough]];
+      case 3:   // the occupancy-targeted single-head kernel
+        return launch_kernel(attention_short_kernel, items, 256, s, qkv, out, S, W, H, causal, q8, qs, rows_pad);
+      case 1:   // non-causal: the resident-K/V kernel with 4 waves (causal: the default below)
+        if (!causal)
+          return launch_kernel<attention_res_kernel<4, false>>(items, 256, res_lds, s, qkv, out, S, W, H, q8, qs, rows_pad);
+        break;
+      default: break;
+    }
   }
 #endif
-  if (!one_wave && !old_flash && !causal && S > 64) {
-    // vision towers (257 / 577 tokens): K/V resident in LDS, no per-chunk barriers
-    const int spad = (S + 31) & ~31;
-    const size_t lds = 2 * (size_t)spad * 128;
+
+  // ---- 3. vision towers (257 / 577 tokens): K/V resident in LDS, no per-chunk barriers
+  if (!one_wave && !stream && !causal && S > 64) {
     // Defaults (scripts/attn_micro.py, r03): S <= 320 (L/14, 257 tokens) attention_res_kernel
     // with 8 waves, one 16-row query tile at a time; S > 320 (L/14@336, 577 tokens) the
     // 32x32x16 kernel with 12 waves, one 32-row block each (2157 us per 1000-frame chunk
-    // against 2392 for attention_res_kernel).  A/B variants (MICLIP_ATTN_VAR): 1 res 8 waves
-    // x 1 tile, 2 res 8 waves x 2 tiles, 3 res 16 waves, 4 r32 8 waves x 2 blocks, 5 r32
-    // 12 waves, 6 / 7 r32 12 waves with a start stagger of 1 / 2 quarter workgroup times,
-    // 8 / 9 r32 timing probes (no K/V load / no exponentials: wrong results), 10 r32 12 waves
-    // with the two-phase K/V load
-#if MICLIP_AB
-    const char* ve = std::getenv("MICLIP_ATTN_VAR");   // A/B
-    int var = ve ? std::atoi(ve) : 0;
-#else
-    int var = 0;
-#endif
+    // against 2392 for attention_res_kernel).  The A/B variants (MICLIP_ATTN_VAR) are the cases below.
+    int var = ab_env_int("MICLIP_ATTN_VAR", 0);
     if (var < 1 || var > 14) var = S > 320 ? 5 : 1;
-    const int64_t rp = ((int64_t)B * S + 1) & ~1;
-    auto set_lds = [&](const void* fn, int slot) -> hipError_t {
-      static bool attr_set[13] = {false, false, false, false, false, false, false, false, false, false, false, false, false};
-      if (attr_set[slot]) return hipSuccess;
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) attr_set[slot] = true;
-      return e;
+    const int vr = S - 16 * ((S + 15) / 16 - 1);   // rows of the last query tile
+    // 11 = 1; 12 / 13 (SPLIT) only for a nearly empty last tile (S % 16 in 1..4) and bf16 output (the merge
+    // has no MX-fp8 store), otherwise 1
+    if (var == 11 || ((var == 12 || var == 13) && !(vr <= 4 && !q8))) var = 1;
+    auto res = [&](auto k, int threads, size_t lds) {
+      return launch_kernel<decltype(k)::value>(items, threads, lds, s, qkv, out, S, W, H, q8, qs, rows_pad);
     };
-    hipError_t e = hipSuccess;
-#define ATT_LAUNCH(SLOT, KERNEL, THREADS, ...)                                  \
-  {                                                                             \
-    if ((e = set_lds((const void*)KERNEL, SLOT)) != hipSuccess) return e;       \
-    hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS), lds, s, __VA_ARGS__);       \
-  }
+    auto r32 = [&](auto k, int threads, int stagger_ticks) {
+      return launch_kernel<decltype(k)::value>(items, threads, res_lds, s, qkv, out, S, W, H, q8, qs, rows_pad,
+                                               stagger_ticks);
+    };
+    switch (var) {
+      case 1: return res(Kern<attention_res_kernel<8, false>>{}, 512, res_lds);    // 8 waves x 1 tile
+      case 5: return r32(Kern<attention_r32_kernel<12, false>>{}, 768, 0);         // 12 waves x 1 block
 #if MICLIP_AB
-    // A/B variant 12: the nearly empty last query tile (S % 16 in 1..4, bf16 output) split over
-    // the 8 waves' key tiles (attention_res_kernel SPLIT).  Measured at L/14 (scripts/attn_micro.py,
-    // r04): 1074 vs 1031 us per 1667-frame chunk -- the second workgroup on the CU already fills
-    // the idle waves -- so the unsplit kernel stays the default.  Variant 11 = variant 1.
-    const int vr = S - 16 * ((S + 15) / 16 - 1);
-    if (var == 12 && vr <= 4 && !q8) {
-      const size_t lds_s = lds + (size_t)8 * vr * 68 * 4;
-      if ((e = set_lds((const void*)attention_res_kernel<8, false, true>, 0)) != hipSuccess) return e;
-      hipLaunchKernelGGL((attention_res_kernel<8, false, true>), grid, dim3(512), lds_s, s, qkv, out, S, W, H, q8, qs,
-                         rp);
-      return hipGetLastError();
-    }
-    if (var == 13 && vr <= 4 && !q8) {   // A/B: the split tile first, then the full tiles, then the merge
-      const size_t lds_s = lds + (size_t)8 * vr * 68 * 4;
-      if ((e = set_lds((const void*)attention_res_kernel<8, false, true, true>, 11)) != hipSuccess) return e;
-      hipLaunchKernelGGL((attention_res_kernel<8, false, true, true>), grid, dim3(512), lds_s, s, qkv, out, S, W, H, q8,
-                         qs, rp);
-      return hipGetLastError();
-    }
-    if (var == 14) {   // A/B: Q fragments one tile ahead
-      if ((e = set_lds((const void*)attention_res_kernel<8, false, false, false, true>, 12)) != hipSuccess) return e;
-      hipLaunchKernelGGL((attention_res_kernel<8, false, false, false, true>), grid, dim3(512), lds, s, qkv, out, S, W,
-                         H, q8, qs, rp);
-      return hipGetLastError();
-    }
-#endif
-    if (var == 11 || var == 12 || var == 13) var = 1;
-    if (var == 1) ATT_LAUNCH(1, (attention_res_kernel<8, false>), 512, qkv, out, S, W, H, q8, qs, rp)
-    else if (var == 5) ATT_LAUNCH(5, (attention_r32_kernel<12, false>), 768, qkv, out, S, W, H, q8, qs, rp, 0)
-#if MICLIP_AB
-    else if (var == 2) ATT_LAUNCH(2, (attention_res_kernel<8, true>), 512, qkv, out, S, W, H, q8, qs, rp)
-    else if (var == 3) ATT_LAUNCH(3, (attention_res_kernel<16, false>), 1024, qkv, out, S, W, H, q8, qs, rp)
-    else if (var == 4) ATT_LAUNCH(4, (attention_r32_kernel<8, true>), 512, qkv, out, S, W, H, q8, qs, rp, 0)
-    else if (var == 6 || var == 7)
-      ATT_LAUNCH(var, (attention_r32_kernel<12, false>), 768, qkv, out, S, W, H, q8, qs, rp, (var - 5) * (S * S / 378))
-    else if (var == 8) ATT_LAUNCH(8, (attention_r32_kernel<12, false, 2>), 768, qkv, out, S, W, H, q8, qs, rp, 0)
-    else if (var == 10) ATT_LAUNCH(10, (attention_r32_kernel<12, false, 0, true>), 768, qkv, out, S, W, H, q8, qs, rp, 0)
-    else ATT_LAUNCH(9, (attention_r32_kernel<12, false, 1>), 768, qkv, out, S, W, H, q8, qs, rp, 0)
+      case 2: return res(Kern<attention_res_kernel<8, true>>{}, 512, res_lds);     // 8 waves x 2 tiles
+      case 3: return res(Kern<attention_res_kernel<16, false>>{}, 1024, res_lds);  // 16 waves
+      case 4: return r32(Kern<attention_r32_kernel<8, true>>{}, 512, 0);           // 8 waves x 2 blocks
+      case 6:
+      case 7:   // 5 with a start stagger of 1 / 2 quarter workgroup times
+        return r32(Kern<attention_r32_kernel<12, false>>{}, 768, (var - 5) * (S * S / 378));
+      case 8: return r32(Kern<attention_r32_kernel<12, false, 2>>{}, 768, 0);      // timing probe: no K/V load (wrong results)
+      case 10: return r32(Kern<attention_r32_kernel<12, false, 0, true>>{}, 768, 0);   // 5 with the two-phase K/V load
+      // 12: the nearly empty last query tile split over the 8 waves' key tiles (attention_res_kernel SPLIT).
+      // Measured at L/14 (scripts/attn_micro.py, r04): 1074 vs 1031 us per 1667-frame chunk -- the second
+      // workgroup on the CU already fills the idle waves -- so the unsplit kernel stays the default.
+      case 12: return res(Kern<attention_res_kernel<8, false, true>>{}, 512, res_lds + (size_t)8 * vr * 68 * 4);
+      // 13: the split tile first, then the full tiles, then the merge
+      case 13: return res(Kern<attention_res_kernel<8, false, true, true>>{}, 512, res_lds + (size_t)8 * vr * 68 * 4);
+      case 14: return res(Kern<attention_res_kernel<8, false, false, false, true>>{}, 512, res_lds);   // Q fragments one tile ahead
+      default: return r32(Kern<attention_r32_kernel<12, false, 1>>{}, 768, 0);     // 9: timing probe, no exponentials (wrong results)
 #else
-    else return hipErrorNotSupported;
+      default: return hipErrorNotSupported;   // (no switch: var is 1 or 5)
 #endif
-#undef ATT_LAUNCH
-    return hipGetLastError();
+    }
   }
+
+  // ---- 4. A/B only: the one-wave kernel, whole padded sequence per wave
 #if MICLIP_AB
-  if (one_wave) {
-    if (S <= 32) hipLaunchKernelGGL(attention_kernel<32>, grid, dim3(64), 0, s, qkv, out, S, W, H, causal, items);
-    else if (S <= 64) hipLaunchKernelGGL(attention_kernel<64>, grid, dim3(64), 0, s, qkv, out, S, W, H, causal, items);
-    else hipLaunchKernelGGL(attention_kernel<96>, grid, dim3(64), 0, s, qkv, out, S, W, H, causal, items);
-    return hipGetLastError();
-  }
+  if (one_wave)
+    return with_value<32, 64, 96>(std::max(32, (S + 31) & ~31), [&](auto sp) {
+      return launch_kernel(attention_kernel<decltype(sp)::value>, items, 64, s, qkv, out, S, W, H, causal, items);
+    });
 #endif
+
+  // ---- 5. flash
   // NT = ceil(tiles / 8) query tiles per wave on 8 waves; S <= 64: one tile on
   // each of 4 waves, single slot.  Fewer waves with fewer idle tile slots
   // measured slower (L/14 257 tokens on 6 waves x 3 tiles: 470 vs 421 us; text
   // 77 on 5 x 1: 45 vs 31 us): a workgroup lasts as long as its busiest wave
   // either way, and 8 waves spread that wave's SIMD over fewer partners.
   const int nqt = (S + 15) / 16;
-  const int64_t rp = ((int64_t)B * S + 1) & ~1;
-#define FLASH(T) \
-  hipLaunchKernelGGL((attention_flash_kernel<T, 1>), grid, dim3(512), 0, s, qkv, out, S, W, H, causal, q8, qs, rp)
   if (nqt <= 4)
-    hipLaunchKernelGGL((attention_flash_kernel<1, 2, 1>), grid, dim3(256), 0, s, qkv, out, S, W, H, causal | (q0only << 11),
-                       q8, qs, rp);
-  else if (nqt <= 8) FLASH(1);
-  else if (nqt <= 16) FLASH(2);
-  else if (nqt <= 24) FLASH(3);
-  else if (nqt <= 32) FLASH(4);
-  else FLASH(5);
-#undef FLASH
-  return hipGetLastError();
+    return launch_kernel(attention_flash_kernel<1, 2, 1>, items, 256, s, qkv, out, S, W, H, causal | q0, q8, qs, rows_pad);
+  return with_value<1, 2, 3, 4, 5>((nqt + 7) / 8, [&](auto nt) {
+    return launch_kernel(attention_flash_kernel<decltype(nt)::value, 1>, items, 512, s, qkv, out, S, W, H, causal, q8, qs,
+                         rows_pad);
+  });
 }
 
 }  // namespace miclip

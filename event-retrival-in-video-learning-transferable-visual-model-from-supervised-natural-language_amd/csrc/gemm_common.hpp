@@ -119,42 +119,17 @@ __device__ __forceinline__ int lane_id() {
 }
 
 // ------------------------------------------------------------------ host: one launch idiom
+// (launch_kernel, with_value and ab_env_int: internal.hpp)
 
 inline int tile_count(const GemmArgs& a, int bm, int bn) { return ((a.M + bm - 1) / bm) * (a.N / bn); }
 // persistent kernels: one workgroup per CU (per `cus` slots), fewer when there are fewer tiles
 inline int persistent_grid(int nt, int cus) { return nt < cus ? nt : cus; }
 
-template <class... P, class... Args>
-hipError_t launch_kernel(void (*kernel)(P...), int grid, int threads, hipStream_t s, const Args&... args) {
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, s, args...);
-  return hipGetLastError();
-}
-
-// A runtime value as a template argument: f(std::integral_constant<int, V>{}) for the V of the
-// list that equals v, hipErrorInvalidValue when v is not in the list.  The list is the
-// instantiation list: a call site names exactly the values its kernel is built for.
-template <int... VS, class F>
-hipError_t with_value(int v, F&& f) {
-  hipError_t r = hipErrorInvalidValue;
-  (void)((v == VS ? (r = f(std::integral_constant<int, VS>{}), true) : false) || ...);
-  return r;
-}
-// ... the epilogue (GemmEpi)
+// with_value for the epilogue (GemmEpi)
 template <int... EPIS, class F>
 hipError_t with_epi(int epi, F&& f) {
   return with_value<EPIS...>(epi, f);
 }
-
-// An A/B build's integer switch MICLIP_* from the environment (unset: fallback); the product build
-// has no switches and takes the fallback at compile time.
-#if MICLIP_AB
-inline int ab_env_int(const char* name, int fallback) {
-  const char* v = std::getenv(name);
-  return v ? std::atoi(v) : fallback;
-}
-#else
-constexpr int ab_env_int(const char*, int fallback) { return fallback; }
-#endif
 
 }  // namespace
 }  // namespace miclip

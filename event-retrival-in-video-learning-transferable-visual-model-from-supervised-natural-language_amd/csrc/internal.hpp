@@ -3,11 +3,74 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
+#include <type_traits>
+
 #ifndef MICLIP_AB   // 1: the A/B build (common.hpp)
 #define MICLIP_AB 0
 #endif
 
 namespace miclip {
+
+// ------------------------------------------------------------------ host: one launch idiom
+// (the kernel families' launchers: gemm*.hip through gemm_common.hpp, attention.hip)
+
+template <class... P, class... Args>
+hipError_t launch_kernel(void (*kernel)(P...), int grid, int threads, hipStream_t s, const Args&... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, s, args...);
+  return hipGetLastError();
+}
+// ... with `lds` bytes of dynamic LDS.  The kernel is a template argument, so each kernel
+// instantiation has its own flag here: its dynamic-LDS limit is raised to 160 KB (the default is
+// 64 KB) once per process, before its first launch; a failure is returned and tried again next time.
+template <auto KERNEL, class... Args>
+hipError_t launch_kernel(int grid, int threads, size_t lds, hipStream_t s, const Args&... args) {
+  static bool raised = false;
+  if (!raised) {
+    const hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    raised = true;
+  }
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(threads), lds, s, args...);
+  return hipGetLastError();
+}
+
+// A runtime value as a template argument: f(std::integral_constant<int, V>{}) for the V of the
+// list that equals v, hipErrorInvalidValue when v is not in the list.  The list is the
+// instantiation list: a call site names exactly the values its kernel is built for.
+template <int... VS, class F>
+hipError_t with_value(int v, F&& f) {
+  hipError_t r = hipErrorInvalidValue;
+  (void)((v == VS ? (r = f(std::integral_constant<int, VS>{}), true) : false) || ...);
+  return r;
+}
+
+// An A/B build's integer switch MICLIP_* from the environment (unset: fallback), read on every
+// call so that a test can switch it within one process; the product build has no switches and
+// takes the fallback at compile time.
+#if MICLIP_AB
+inline int ab_env_int(const char* name, int fallback) {
+  const char* v = std::getenv(name);
+  return v ? std::atoi(v) : fallback;
+}
+#else
+constexpr int ab_env_int(const char*, int fallback) { return fallback; }
+#endif
+
+// Switches that ride in attention()'s `flags` beside the causal bit (values fixed by the C ABI:
+// mi_op_attention passes its `causal` argument through, and accepts the first three).
+enum AttnFlags {
+  ATT_CAUSAL = 1,        // causal mask (the text tower); every kernel but the resident-K/V ones, which
+                         // are non-causal only (a causal call never reaches them)
+  ATT_ONE_WAVE = 0x100,  // S <= 96, bf16 output: the one-wave-per-head attention_kernel.  A/B build only:
+                         // the product build answers hipErrorNotSupported
+  ATT_STREAM = 0x200,    // S > 64 non-causal: the chunk-streaming attention_flash_kernel instead of the
+                         // resident-K/V kernels (parity tests of both paths); no effect elsewhere
+  ATT_Q0_ONLY = 0x800    // only the first query tile's rows are computed and written (the last vision
+                         // block, read at its CLS rows alone): honoured by the S <= 64 flash kernel
+                         // (16 rows) and by precise.hip's f32 kernels (32 rows); every other kernel
+                         // computes all rows
+};
 
 enum GemmEpi {
   EPI_BF16 = 0,        // out bf16 = acc + bias
@@ -201,8 +264,8 @@ hipError_t residual_ln(float* x, const uint16_t* delta, int64_t stride, int writ
 hipError_t im2col(const void* pixels, int in_bf16, uint16_t* out, int B, int R, int P, int Kp,
                   hipStream_t s);
 // multi-head attention over qkv [B*S, 3W] bf16 -> out [B*S, W] bf16, head dim 64
-// q8 != nullptr: MX-fp8 output (one 64-k block per head) instead of bf16 out
-hipError_t attention(const uint16_t* qkv, uint16_t* out, int B, int S, int W, int causal,
+// q8 != nullptr: MX-fp8 output (one 64-k block per head) instead of bf16 out; flags: AttnFlags
+hipError_t attention(const uint16_t* qkv, uint16_t* out, int B, int S, int W, int flags,
                      hipStream_t s, uint8_t* q8 = nullptr, uint8_t* qs = nullptr);
 // y [rows, D] f32 -> out (f32/bf16/f16), optional L2 normalisation
 hipError_t finalize_rows(const float* y, void* out, int out_dtype, int rows, int D, int l2,

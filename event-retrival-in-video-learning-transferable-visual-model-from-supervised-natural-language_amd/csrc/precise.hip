@@ -434,9 +434,9 @@ __global__ __launch_bounds__(256, MINB) void attn_f32_mfma_kernel(const float* _
   const int H = W / 64;
   const int item = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: SGPR descriptors)
   if (item >= nseq * H) return;
-  // causal bit 11: the first 32-query block only (the last vision block: outputs read at the CLS rows)
-  const int qend = ((causal >> 11) & 1) ? min(S, 32) : S;
-  causal &= 1;
+  // ATT_Q0_ONLY (internal.hpp): the first 32-query block only (the last vision block: outputs read at the CLS rows)
+  const int qend = (causal & ATT_Q0_ONLY) ? min(S, 32) : S;
+  causal &= ATT_CAUSAL;
   const int bseq = item / H, head = item % H;
   const int64_t ld = 3 * (int64_t)W;
   const float* base = qkv + (int64_t)bseq * S * ld + head * 64;
@@ -553,8 +553,8 @@ __global__ __launch_bounds__(256, 2) void attn_f32_mfma_b_kernel(const float* __
   const int H = W / 64;
   const int item = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform)
   if (item >= nseq * H) return;
-  const int qend = ((causal >> 11) & 1) ? min(S, 32) : S;   // (bit 11: the first query block only)
-  causal &= 1;
+  const int qend = (causal & ATT_Q0_ONLY) ? min(S, 32) : S;   // (ATT_Q0_ONLY: the first query block only)
+  causal &= ATT_CAUSAL;
   const int bseq = item / H, head = item % H;
   const int ld = 3 * W;
   auto rho = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
@@ -696,8 +696,8 @@ __global__ __launch_bounds__(256, 2) void attn_f32s_kernel(const float* __restri
   const int H = W / 64;
   const int item = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform)
   if (item >= nseq * H) return;
-  const int qend = ((causal >> 11) & 1) ? min(S, 32) : S;   // (bit 11: the first query block only)
-  causal &= 1;
+  const int qend = (causal & ATT_Q0_ONLY) ? min(S, 32) : S;   // (ATT_Q0_ONLY: the first query block only)
+  causal &= ATT_CAUSAL;
   const int bseq = item / H, head = item % H;
   const int ld = 3 * W;
   auto rho = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
@@ -906,8 +906,8 @@ __global__ __launch_bounds__(256, MINB) void attn_f32_mfma_pre_kernel(const floa
   const int H = W / 64;
   const int item = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: SGPR descriptors)
   if (item >= nseq * H) return;
-  const int qend = ((causal >> 11) & 1) ? min(S, 32) : S;   // (bit 11: the first query block only)
-  causal &= 1;
+  const int qend = (causal & ATT_Q0_ONLY) ? min(S, 32) : S;   // (ATT_Q0_ONLY: the first query block only)
+  causal &= ATT_CAUSAL;
   const int bseq = item / H, head = item % H;
   const int ld = 3 * W;
   auto rho = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
@@ -1150,8 +1150,8 @@ static int attn_f32_variant() {
 hipError_t attention_f32(const float* qkv, float* out, int B, int S, int W, int causal, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (W % 64 || S < 1) return hipErrorInvalidValue;
-  const int cq = causal;   // (bit 11: the first query block only, MFMA kernels; the scalar kernels compute all)
-  causal &= 1;
+  const int cq = causal;   // (with ATT_Q0_ONLY: the first query block only, MFMA kernels; the scalar kernels compute all)
+  causal &= ATT_CAUSAL;
   const dim3 grid((unsigned)B * (W / 64));
   const dim3 grid4((unsigned)(((int64_t)B * (W / 64) + 3) / 4));
 #if MICLIP_AB

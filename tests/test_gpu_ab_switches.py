@@ -1,4 +1,4 @@
-"""The A/B switches of the encoder orchestration (api.cpp ab_int) that no other test sets, one
+"""The A/B switches of the encoder orchestration (internal.hpp ab_env_int) that no other test sets, one
 at a time through the A/B library and all inside this one process: the library reads a switch on
 every call (MICLIP_F32_SPLIT when a context is created), so each case runs the tower code behind
 its switch although earlier cases and tests already ran the library with the defaults.

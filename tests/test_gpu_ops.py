@@ -510,6 +510,81 @@ def test_attention_split_last_tile(gpu, monkeypatch, B, S, W):
     assert (a.double() - ref)[~full].abs().max().item() <= 2 * err_b + 2e-3
 
 
+def _attention_ref64(qkv, B, S, W, causal):
+    import torch
+    x = qkv.double().reshape(B, S, 3, W // 64, 64)
+    q, k, v = (x[:, :, i].transpose(1, 2) for i in range(3))
+    s = q @ k.transpose(-1, -2) * 0.125
+    if causal:
+        s = s.masked_fill(torch.triu(torch.ones(S, S, dtype=torch.bool, device=qkv.device), 1), float("-inf"))
+    return (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(B * S, W)
+
+
+@pytest.mark.parametrize("kind,B,S,W,causal",
+                         [("short", B, S, W, c) for (B, S, W) in [(3, 50, 128), (2, 17, 192), (1, 64, 64)]
+                          for c in (0, 1)] +
+                         [("pipe", 130, 50, 128, 0)] +
+                         [("var", 2, 257, 128, 0), ("var", 2, 97, 128, 0), ("var", 1, 130, 64, 0),
+                          ("var", 1, 577, 64, 0)] +
+                         [("var12", 2, 100, 128, 0), ("var12", 2, 104, 128, 0)])
+def test_attention_ab_variants_run(gpu, monkeypatch, kind, B, S, W, causal):
+    """Every value of the A/B build's attention switches that no other test sets reaches a kernel
+    that computes attention: each output against the float64 softmax at test_attention's bound, and
+    bit-identical to its baseline where attention.hip says the variant changes no arithmetic.
+      short (S <= 64, MICLIP_ATTN_SHORT): 2 (two heads per workgroup; odd H falls to the single-head
+        kernel), 3 (occupancy target), 6 (batched V^T reads) and 51 (persistent workgroups, one per
+        CU) equal the unset run; 1 (the resident-K/V kernel on 4 waves) is another kernel: float64.
+      pipe: 51 with 260 items, more than one per CU, so a workgroup walks on to a prefetched item.
+      var (S > 64, MICLIP_ATTN_VAR): 14 (Q prefetch) = 11, 13 (split tile first) = 12, 7 (stagger) = 5;
+        8 and 9 are timing probes with wrong results by design: they only have to run.
+      var12: 12 with S % 16 = 4 (split) and = 8 (no split: variant 1, bit-identical to 11)."""
+    import torch
+    N_ = _lib()
+    La = N_.lib_ab()
+    g = torch.Generator(device="cpu").manual_seed(B * S + W + causal)
+    qkv = (torch.randn(B * S, 3 * W, generator=g) * 1.5).bfloat16().to(gpu)
+    ref = _attention_ref64(qkv, B, S, W, causal)
+    tol = 3e-2 * max(1.0, ref.abs().max().item())
+
+    def run(name, value, check=True):
+        if value is None:
+            monkeypatch.delenv(name, raising=False)
+        else:
+            monkeypatch.setenv(name, value)
+        out = torch.full((B * S, W), float("nan"), dtype=torch.bfloat16, device=gpu)
+        assert La.mi_op_attention(qkv.data_ptr(), out.data_ptr(), B, S, W, causal, _stream()) == 0, La.mi_last_error()
+        torch.cuda.synchronize()
+        if check:
+            err = (out.double() - ref).abs().max().item()
+            print(f"{name}={value}: max err {err} (tol {tol})")
+            assert err < tol, f"{name}={value}: max err {err} (tol {tol})"     # (a NaN left in the output fails too)
+        return out
+
+    if kind == "short":
+        base = run("MICLIP_ATTN_SHORT", None)
+        for v in ("2", "3", "6", "51"):
+            assert torch.equal(run("MICLIP_ATTN_SHORT", v), base), f"MICLIP_ATTN_SHORT={v} differs from the default"
+        run("MICLIP_ATTN_SHORT", "1")
+    elif kind == "pipe":
+        cus = torch.cuda.get_device_properties(gpu).multi_processor_count
+        if B * (W // 64) <= cus:
+            pytest.skip(f"{B * (W // 64)} items on {cus} CUs: no workgroup walks a second item")
+        base = run("MICLIP_ATTN_SHORT", None)
+        assert torch.equal(run("MICLIP_ATTN_SHORT", "51"), base)
+    elif kind == "var":
+        outs = {v: run("MICLIP_ATTN_VAR", str(v)) for v in (5, 7, 11, 12, 13, 14)}
+        assert torch.equal(outs[14], outs[11]), "variant 14 differs from 11"
+        assert torch.equal(outs[13], outs[12]), "variant 13 differs from 12"
+        assert torch.equal(outs[7], outs[5]), "variant 7 differs from 5"
+        for v in (8, 9):
+            run("MICLIP_ATTN_VAR", str(v), check=False)
+    else:
+        a = run("MICLIP_ATTN_VAR", "12")
+        b = run("MICLIP_ATTN_VAR", "11")
+        if S - 16 * ((S + 15) // 16 - 1) > 4:
+            assert torch.equal(a, b), "variant 12 without a split differs from 11"
+
+
 @pytest.mark.parametrize("M,N,K,epi", [(1, 64, 32, 0), (100, 128, 64, 1), (513, 384, 768, 2), (3000, 3072, 768, 1),
                                        (777, 768, 3072, 2), (50, 512, 768, 3), (20000, 2304, 768, 0)])
 def test_gemm_f32(gpu, M, N, K, epi):
