@@ -963,7 +963,7 @@ __global__ __launch_bounds__(NW * 64) void attention_r32_kernel(const uint16_t* 
           for (int kt = 0; kt < NKB; ++kt)
 #pragma unroll
             for (int i = 0; i < 16; ++i)
-              if (c * 64 + kt * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh >= S) x[u][kt][i] = -INFINITY;
+              if (c * 64 + kt * 32 + c_row(i, hh) >= S) x[u][kt][i] = -INFINITY;
         }
         float cm = x[u][0][0];
 #pragma unroll

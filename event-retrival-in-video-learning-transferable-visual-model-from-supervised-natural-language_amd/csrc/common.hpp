@@ -64,6 +64,10 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Row of a 32x32 MFMA C fragment that register rg (0..15) of a lane in half h (lane >> 5) holds;
+// the column is lane & 31.
+__device__ __forceinline__ constexpr int c_row(int rg, int h) { return (rg & 3) + 8 * (rg >> 2) + 4 * h; }
+
 // async 16-byte global -> LDS copy: LDS destination is lds_base + lane*16
 // (wave-uniform base), the global source is per lane.
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_base) {

@@ -16,8 +16,8 @@ namespace miclip {
 // (the kernel families' launchers: gemm*.hip through gemm_common.hpp, attention.hip)
 
 template <class... P, class... Args>
-hipError_t launch_kernel(void (*kernel)(P...), int grid, int threads, hipStream_t s, const Args&... args) {
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, s, args...);
+hipError_t launch_kernel(void (*kernel)(P...), dim3 grid, int threads, hipStream_t s, const Args&... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, s, args...);
   return hipGetLastError();
 }
 // ... with `lds` bytes of dynamic LDS.  The kernel is a template argument, so each kernel

@@ -14,8 +14,6 @@
 //   ln_f32     LayerNorm rows in f32 -> f32 (optionally the EOT row of each token row)
 //   attn_f32   softmax(q k^T / 8 [+ causal]) v per (sequence, head), f32
 //   im2col_f32 conv1 patches in f32
-#include <cstdlib>
-
 #include "common.hpp"
 #include "internal.hpp"
 
@@ -101,7 +99,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
       __syncthreads();
     }
   }
-  // epilogue: C layout col = lane & 31, row = (q & 3) + 8 (q >> 2) + 4 h
+  // epilogue: C layout col = lane & 31, row = c_row(q, h)
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
     const int n = n0 + 64 * wn + 32 * b + r;
@@ -111,12 +109,12 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
     for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const int m = m0 + 64 * wm + 32 * a + (q & 3) + 8 * (q >> 2) + 4 * h;
+        const int m = m0 + 64 * wm + 32 * a + (q & 3) + 8 * (q >> 2) + 4 * h;   // (c_row(q, h), written out: see profiles/precise_attn_isa.log)
         if (m >= M) continue;
         const int64_t orow = group ? (int64_t)(m / group) * gstride + goffset + m % group : m;
         float v = acc[a][b][q] + bv;
         float* o = out + orow * ldo + n;
-        if (EPI == EPI_GELU_BF16) v = v * (1.0f / (1.0f + expf(-1.702f * v)));   // QuickGELU x * sigmoid(1.702 x)
+        if (EPI == EPI_GELU_BF16) v = quick_gelu_f32(v);
         if (EPI == EPI_RELU_F32) v = fmaxf(v, 0.f);
         if (EPI == EPI_RESID_F32) *o = *o + v;
         else *o = v;
@@ -146,12 +144,7 @@ __global__ __launch_bounds__(256) void split6_kernel(const float* __restrict__ x
   const int64_t r = i / k4;
   const int c = (int)(i - r * k4) * 4;
   float4 v = *(const float4*)(x + r * ldx + c);
-  if (gelu) {
-    v.x = v.x * (1.0f / (1.0f + expf(-1.702f * v.x)));
-    v.y = v.y * (1.0f / (1.0f + expf(-1.702f * v.y)));
-    v.z = v.z * (1.0f / (1.0f + expf(-1.702f * v.z)));
-    v.w = v.w * (1.0f / (1.0f + expf(-1.702f * v.w)));
-  }
+  if (gelu) v = make_float4(quick_gelu_f32(v.x), quick_gelu_f32(v.y), quick_gelu_f32(v.z), quick_gelu_f32(v.w));
   u16 p[3][4];
   split3(v.x, p[0][0], p[1][0], p[2][0]);
   split3(v.y, p[0][1], p[1][1], p[2][1]);
@@ -340,12 +333,12 @@ __global__ __launch_bounds__(256) void ln_f32_kernel(const float* __restrict__ x
 }
 
 // ------------------------------------------------------------- attention
-// One workgroup per (sequence, head); a thread owns one query row (q scaled
-// by 1/8 = head_dim^-1/2, exact), keys and values stream through LDS in
-// chunks of 64 with an online softmax (per-chunk max, one rescale per chunk).
-template <int NT>
-__global__ __launch_bounds__(NT) void attn_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int S,
-                                                      int W, int causal) {
+// S > 128 (B/16's 197 tokens, L/14's 257 and 577).  One workgroup of 256 threads per (sequence,
+// head); a thread owns one query row (q scaled by 1/8 = head_dim^-1/2, exact), keys and values
+// stream through LDS in chunks of 64 with an online softmax (per-chunk max, one rescale per chunk).
+__global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int S,
+                                                       int W, int causal) {
+  constexpr int NT = 256;
   __shared__ float Ks[64 * 64];
   __shared__ float Vs[64 * 64];
   const int H = W / 64;
@@ -409,48 +402,156 @@ __global__ __launch_bounds__(NT) void attn_f32_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------- attention (MFMA)
-// S <= 32 NKT (<= 128: B/32's 50 tokens, the text tower's 77): one wave per (sequence, head),
-// every operand in registers, on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32: exact products,
-// f32 accumulation, as fmaf chains).  The 32x32 C layout puts column (lane & 31) in the lane
-// and rows rho(r, h) = (r & 3) + 8 (r >> 2) + 4 h, h = lane >> 5, in its registers r = 0..15.
+// S <= 128 (B/32's 50 tokens, the text tower's 77): one wave per (sequence, head), every operand
+// in registers.  The 32x32 C layout puts column (lane & 31) in the lane and rows c_row(r, h),
+// h = lane >> 5, in its registers r = 0..15 (common.hpp).
 //   S^T = K Q^T per key tile kt and 32-query block: A = K (lane (key i, h) gives K[i][32 h + s]
 //     at step s), B = Q (lane (query j, h) gives q[j][32 h + s] / 8): lane (query j, h) then
-//     holds its query's scores against keys rho(r, h) -- the softmax over keys is in-lane over
+//     holds its query's scores against keys c_row(r, h) -- the softmax over keys is in-lane over
 //     16 NKT values plus the partner lane j + 32.
-//   O = P V per 32-dim tile dt: A = P, and the k pair of step s is keys {rho(s, 0), rho(s, 1)},
+//   O = P V per 32-dim tile dt: A = P, and the k pair of step s is keys {c_row(s, 0), c_row(s, 1)},
 //     so lane (query i, h) gives its own register s (no data movement); B = V (lane (dim j, h)
-//     gives V[rho(s, h)][32 dt + j]).  C: lane (dim j, h) holds queries rho(r, h), so each
+//     gives V[c_row(s, h)][32 dt + j]).  C: lane (dim j, h) holds queries c_row(r, h), so each
 //     register's 32 lanes store one 128-byte row segment.
-// Replaces attn_f32_kernel (a thread per query row, scalar fmaf over LDS; 10.4 ms per B/32 layer
-// at 10k frames, profiles/r05_a_fp32_bench_kernel_stats.csv).
-// CL: loads and stores through buffer descriptors whose range ends at the sequence's last row, so
-// the padding rows read zeros and their stores drop with no branch (a conditional load or store
-// compiles to an exec-masked branch around each one: 119 branches per wave and SGPR spills through
-// v_writelane in the NKT = 2 kernel); the same values, bit-identical
+// Three kernels are built on this layout: attn_f32_mfma_kernel and attn_f32_mfma_b_kernel on the
+// exact-f32 MFMA (v_mfma_f32_32x32x2_f32: exact products, f32 accumulation, as fmaf chains) and
+// attn_f32s_kernel on the f16 MFMA over split operands.  Their pieces are defined once below.  The
+// two product kernels keep some of them written out, each with a comment naming the piece: through
+// the shared definition hipcc's code for them changed (profiles/precise_attn_isa.log lists the
+// sites and the forms tried).
+typedef unsigned int u32x4_s __attribute__((ext_vector_type(4)));
+
+// Word 3 of the raw buffer descriptors (stride 0: an access at or past the byte range reads zero
+// or is dropped): DATA_FORMAT = 32 bits, nothing else set
+constexpr int RSRC_FLAGS = 0x00020000;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, bytes, RSRC_FLAGS);
+}
+
+// The wave's item of the grid's walk over (sequence, head) pairs, four waves a workgroup
+// (wave-uniform: descriptors and column bases stay in SGPRs); a kernel returns at item >= nseq * H
+__device__ __forceinline__ int wave_item() { return blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+
+// What a wave knows about its item.  rin / rout: the sequence's rows of qkv [S][3 W] / of out
+// [S][W]; their range ends at the sequence's last row, so the padding rows of a 32-row tile read
+// zeros and their stores drop with no branch (a conditional load or store compiles to an
+// exec-masked branch around each one: 119 branches per wave and SGPR spills through v_writelane
+// in the NKT = 2 kernel).  Offsets are from the sequence's first row.
+struct AttnWave {
+  int j, h;          // lane & 31, lane >> 5
+  int S, W, ld;      // ld = 3 W, qkv's row stride
+  int bseq, head;
+  int qend;          // queries [0, qend): S, or with ATT_Q0_ONLY (internal.hpp) the first 32-query block
+                     // only (the last vision block: outputs read at the CLS rows)
+  int causal;        // the ATT_CAUSAL bit alone
+  __amdgpu_buffer_rsrc_t rin, rout;
+};
+__device__ __forceinline__ AttnWave attn_wave(int item, const float* qkv, float* out, int S, int W, int flags) {
+  AttnWave w;
+  const int lane = threadIdx.x & 63, H = W / 64;
+  w.j = lane & 31;
+  w.h = lane >> 5;
+  w.qend = (flags & ATT_Q0_ONLY) ? min(S, 32) : S;
+  w.causal = flags & ATT_CAUSAL;
+  w.bseq = item / H;
+  w.head = item % H;
+  w.S = S;
+  w.W = W;
+  w.ld = 3 * W;
+  w.rin = make_rsrc(qkv + (int64_t)w.bseq * S * w.ld, S * w.ld * 4);
+  w.rout = make_rsrc(out + (int64_t)w.bseq * S * W, S * W * 4);
+  return w;
+}
+
+// The loaders and the store below put rows in the per-lane offset and a column block cb in the
+// scalar offset, which the range check does not see (the batched and the split kernel).
+
+// Row r's 32 columns cb + 32 h .. + 31, times mul: Q (cb = head * 64, mul = 1/8) and K (cb = W +
+// head * 64) as MFMA operands
+__device__ __forceinline__ void ld_row32(AttnWave w, int r, int cb, float* v, float mul = 1.0f) {
+  const uint32_t vo = (uint32_t)((r * w.ld + 32 * w.h) * 4);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const u32x4_s t = __builtin_bit_cast(u32x4_s, __builtin_amdgcn_raw_buffer_load_b128(w.rin, vo + 16 * c, cb * 4, 0));
+    v[4 * c] = __uint_as_float(t[0]) * mul; v[4 * c + 1] = __uint_as_float(t[1]) * mul;
+    v[4 * c + 2] = __uint_as_float(t[2]) * mul; v[4 * c + 3] = __uint_as_float(t[3]) * mul;
+  }
+}
+
+// V[key kt * 32 + c_row(st, h)][cb + j]: with cb = 2 W + head * 64 + 32 dt, the B operand of step
+// st of O = P V for key tile kt and dim tile dt
+__device__ __forceinline__ float ld_v(AttnWave w, int kt, int st, int cb) {
+  const int key = kt * 32 + (st & 3) + 8 * (st >> 2) + 4 * w.h;   // (c_row written out: profiles/precise_attn_isa.log)
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(w.rin, (uint32_t)((key * w.ld + w.j) * 4), cb * 4, 0));
+}
+
+// O's fragment of query block q0 (lane (dim j, h): queries q0 + c_row(r, h)) to out's columns
+// cb + j as (o * mul) / l, inv = 1 / l of this lane's query in the S^T layout
+__device__ __forceinline__ void store_o32(AttnWave w, f32x16 o, float inv, int q0, int cb, float mul = 1.0f) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int qr = q0 + c_row(r, w.h);
+    const float iv = __shfl(inv, c_row(r, w.h), 64);   // 1 / l of query c_row(r, h) (held by lane c_row(r, h))
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((o[r] * mul) * iv), w.rout, (uint32_t)((qr * w.W + w.j) * 4),
+                                          cb * 4, 0);
+  }
+}
+
+// The softmax of query qi over the S^T registers (keys kt * 32 + c_row(r, h), with lane ^ 32):
+// masks, max, sc = exp(sc - max); returns 1 / sum.
+template <int NKT>
+__device__ __forceinline__ float softmax_keys(f32x16 (&sc)[NKT], AttnWave w, int qi) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = kt * 32 + c_row(r, w.h);
+      if (key >= w.S || (w.causal && key > qi)) sc[kt][r] = -INFINITY;
+      m = fmaxf(m, sc[kt][r]);
+    }
+  m = fmaxf(m, __shfl_xor(m, 32, 64));
+  float l = 0.f;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float p = expf(sc[kt][r] - m);   // masked keys: exp(-inf) = 0
+      sc[kt][r] = p;
+      l += p;
+    }
+  l += __shfl_xor(l, 32, 64);
+  return 1.0f / l;
+}
+
+// The general kernel, S <= 32 NKT: hipcc places each load next to its first use.  The product's
+// kernel for 64 < S <= 128 (NKT 3, 4); S > 128 runs attn_f32_kernel (a thread per query row, scalar
+// fmaf over LDS), which this form replaced at S <= 128 (10.4 ms per B/32 layer at 10k frames,
+// profiles/r05_a_fp32_bench_kernel_stats.csv).
+// CL = false (A/B MICLIP_ATTN_F32_V=1): plain pointers and a condition per padding row instead of
+// the descriptors -- the same values by independent addressing, bit-identical.  Both forms address
+// an element alike, the whole column in the per-lane offset: this kernel's loads and stores are
+// its own (ld4 / ld1 below, not ld_row32 / ld_v / store_o32).
 template <int NKT, int MINB = 1, bool CL = true>
 __global__ __launch_bounds__(256, MINB) void attn_f32_mfma_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                             int nseq, int S, int W, int causal) {
   const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-  const int H = W / 64;
-  const int item = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: SGPR descriptors)
+  const int H = W / 64, item = wave_item();
   if (item >= nseq * H) return;
-  // ATT_Q0_ONLY (internal.hpp): the first 32-query block only (the last vision block: outputs read at the CLS rows)
+  // (attn_wave written out: profiles/precise_attn_isa.log)
   const int qend = (causal & ATT_Q0_ONLY) ? min(S, 32) : S;
   causal &= ATT_CAUSAL;
   const int bseq = item / H, head = item % H;
   const int64_t ld = 3 * (int64_t)W;
   const float* base = qkv + (int64_t)bseq * S * ld + head * 64;
   float* obase = out + (int64_t)bseq * S * W + head * 64;
-  auto rho = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
-  // (CL: p's row r is passed too; offsets from the sequence's first row, rows >= S out of range)
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(qkv + (int64_t)bseq * S * ld), (short)0, S * (int)ld * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(out + (int64_t)bseq * S * W), (short)0, S * W * 4, 0x00020000);
+  auto rho = [&](int r) { return c_row(r, h); };
+  const __amdgpu_buffer_rsrc_t rin = make_rsrc(qkv + (int64_t)bseq * S * ld, S * (int)ld * 4);
+  const __amdgpu_buffer_rsrc_t rout = make_rsrc(out + (int64_t)bseq * S * W, S * W * 4);
+  // (CL: p's row r and column are passed too)
   auto ld4 = [&](const float* p, bool ok, int r, int col) {
     if (CL) {
-      typedef unsigned int u32x4a __attribute__((ext_vector_type(4)));
-      const u32x4a t = __builtin_bit_cast(u32x4a, __builtin_amdgcn_raw_buffer_load_b128(rin, (uint32_t)((r * (int)ld + col) * 4), 0, 0));
+      const u32x4_s t = __builtin_bit_cast(u32x4_s, __builtin_amdgcn_raw_buffer_load_b128(rin, (uint32_t)((r * (int)ld + col) * 4), 0, 0));
       return make_float4(__uint_as_float(t[0]), __uint_as_float(t[1]), __uint_as_float(t[2]), __uint_as_float(t[3]));
     }
     return ok ? *(const float4*)p : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -486,7 +587,7 @@ __global__ __launch_bounds__(256, MINB) void attn_f32_mfma_kernel(const float* _
 #pragma unroll
       for (int st = 0; st < 32; ++st) sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[st], qv[st], sc[kt], 0, 0, 0);
     }
-    // masks and the softmax statistics of query qi (keys rho(r, h) of every tile, with lane ^ 32)
+    // (softmax_keys written out: profiles/precise_attn_isa.log)
     float m = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
@@ -517,7 +618,7 @@ __global__ __launch_bounds__(256, MINB) void attn_f32_mfma_kernel(const float* _
         float vv[16];
 #pragma unroll
         for (int st = 0; st < 16; ++st) {
-          const int key = kt * 32 + (st & 3) + 8 * (st >> 2) + 4 * h;
+          const int key = kt * 32 + (st & 3) + 8 * (st >> 2) + 4 * h;   // (c_row(st, h) in ld_v's association)
           vv[st] = ld1(base + 2 * W + (int64_t)min(key, S - 1) * ld + 32 * dt + j, key < S, key, 2 * W + head * 64 + 32 * dt + j);
         }
 #pragma unroll
@@ -526,7 +627,7 @@ __global__ __launch_bounds__(256, MINB) void attn_f32_mfma_kernel(const float* _
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int qr = q0 + rho(r);
-        const float iv = __shfl(inv, rho(r), 64);   // 1 / l of query rho(r) (held by lane rho(r))
+        const float iv = __shfl(inv, rho(r), 64);   // 1 / l of query rho(r), as store_o32
         if (CL)
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[r] * iv), rout, (uint32_t)((qr * W + head * 64 + 32 * dt + j) * 4), 0, 0);
         else if (qr < S)
@@ -536,61 +637,35 @@ __global__ __launch_bounds__(256, MINB) void attn_f32_mfma_kernel(const float* _
   }
 }
 
-// The S <= 64 form with its loads batched (round 6; B/32's 50 tokens, the fp32 tower's attention).
-// attn_f32_mfma_kernel above lets hipcc place each load next to its first use: at two waves per
-// SIMD its scheduler keeps two of a key tile's eight K loads in flight and issues V one MFMA ahead,
-// so a wave waits for ~20 dependent L2 round trips per query block.  Here each query block issues
-// Q, both key tiles' K and the first dim tile's V (8 + 16 + 32 loads) together, then a scheduling
-// barrier; the second dim tile's V goes out after the softmax, ahead of the first dim tile's MFMAs.
-// Rows stay in the per-lane offset (rows >= S read zeros and drop their stores by the descriptor's
-// range, which the scalar offset does not enter); the head's column base is the scalar offset.
-// Same MFMAs in the same order, masks, expf and stores: bit-identical to attn_f32_mfma_kernel<2>
-// (tests/test_gpu_ops.py::test_attention_f32_batched_bit_identical).
+#if MICLIP_AB
+// The S <= 64 form with its loads batched (round 6; A/B MICLIP_ATTN_F32_V=4, the exact-f32
+// reference of the product's split-f16 kernel).  attn_f32_mfma_kernel above lets hipcc place each
+// load next to its first use: at two waves per SIMD its scheduler keeps two of a key tile's eight K
+// loads in flight and issues V one MFMA ahead, so a wave waits for ~20 dependent L2 round trips per
+// query block.  Here each query block issues Q, both key tiles' K and the first dim tile's V (8 +
+// 16 + 32 loads) together, then a scheduling barrier; the second dim tile's V goes out after the
+// softmax, ahead of the first dim tile's MFMAs.  Rows stay in the per-lane offset; the head's
+// column base is the scalar offset.  Same MFMAs in the same order, masks, expf and stores:
+// bit-identical to attn_f32_mfma_kernel<2> (tests/test_gpu_ops.py::test_attention_f32_batched_bit_identical).
+// (Every load of a (sequence, head) ahead of its first MFMA, one wave per SIMD at 350 VGPRs, measured
+// slower: 2754 vs 2365 us at 10k B/32 frames, profiles/r06_n_attn_f32_micro.log.)
 __global__ __launch_bounds__(256, 2) void attn_f32_mfma_b_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                 int nseq, int S, int W, int causal) {
   constexpr int NKT = 2;
-  const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-  const int H = W / 64;
-  const int item = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform)
+  const int H = W / 64, item = wave_item();
   if (item >= nseq * H) return;
-  const int qend = (causal & ATT_Q0_ONLY) ? min(S, 32) : S;   // (ATT_Q0_ONLY: the first query block only)
-  causal &= ATT_CAUSAL;
-  const int bseq = item / H, head = item % H;
-  const int ld = 3 * W;
-  auto rho = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(qkv + (int64_t)bseq * S * ld), (short)0, S * ld * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(out + (int64_t)bseq * S * W), (short)0, S * W * 4, 0x00020000);
-  typedef unsigned int u32x4a __attribute__((ext_vector_type(4)));
-  // row r's 32 columns 32 h .. 32 h + 31 of the block at column cb (Q: head * 64, K: W + head * 64)
-  auto ld_row32 = [&](int r, int cb, float* v, float mul) {
-    const uint32_t vo = (uint32_t)((r * ld + 32 * h) * 4);
+  const AttnWave w = attn_wave(item, qkv, out, S, W, causal);
+  const int qcol = w.head * 64, kcol = W + qcol, vcol = 2 * W + qcol;
+  for (int q0 = 0; q0 < w.qend; q0 += 32) {
+    const int qi = q0 + w.j;   // this lane's query in the S^T layout
+    float qv[32], kv[NKT][32], vv[2][NKT][16];
+    ld_row32(w, qi, qcol, qv, 0.125f);
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const u32x4a t = __builtin_bit_cast(u32x4a, __builtin_amdgcn_raw_buffer_load_b128(rin, vo + 16 * c, cb * 4, 0));
-      v[4 * c] = __uint_as_float(t[0]) * mul; v[4 * c + 1] = __uint_as_float(t[1]) * mul;
-      v[4 * c + 2] = __uint_as_float(t[2]) * mul; v[4 * c + 3] = __uint_as_float(t[3]) * mul;
-    }
-  };
-  // V[key rho(st, h) of key tile kt][32 dt + j], the B operand of step st
-  auto ld_v = [&](int dt, float (&vv)[NKT][16]) {
+    for (int kt = 0; kt < NKT; ++kt) ld_row32(w, kt * 32 + w.j, kcol, kv[kt]);
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
-      for (int st = 0; st < 16; ++st) {
-        const int key = kt * 32 + (st & 3) + 8 * (st >> 2) + 4 * h;
-        vv[kt][st] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-            rin, (uint32_t)((key * ld + j) * 4), (2 * W + head * 64 + 32 * dt) * 4, 0));
-      }
-  };
-  for (int q0 = 0; q0 < qend; q0 += 32) {
-    const int qi = q0 + j;   // this lane's query in the S^T layout
-    float qv[32], kv[NKT][32], v0[NKT][16], v1[NKT][16];
-    ld_row32(qi, head * 64, qv, 0.125f);
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) ld_row32(kt * 32 + j, W + head * 64, kv[kt], 1.0f);
-    ld_v(0, v0);
+      for (int st = 0; st < 16; ++st) vv[0][kt][st] = ld_v(w, kt, st, vcol);
     __builtin_amdgcn_sched_barrier(0);
     f32x16 sc[NKT];
 #pragma unroll
@@ -600,28 +675,11 @@ __global__ __launch_bounds__(256, 2) void attn_f32_mfma_b_kernel(const float* __
 #pragma unroll
       for (int st = 0; st < 32; ++st) sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[kt][st], qv[st], sc[kt], 0, 0, 0);
     }
-    float m = -INFINITY;
+    const float inv = softmax_keys(sc, w, qi);
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = kt * 32 + rho(r);
-        if (key >= S || (causal && key > qi)) sc[kt][r] = -INFINITY;
-        m = fmaxf(m, sc[kt][r]);
-      }
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float l = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p = expf(sc[kt][r] - m);   // masked keys: exp(-inf) = 0
-        sc[kt][r] = p;
-        l += p;
-      }
-    l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
-    ld_v(1, v1);
+      for (int st = 0; st < 16; ++st) vv[1][kt][st] = ld_v(w, kt, st, vcol + 32);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) {
@@ -630,19 +688,13 @@ __global__ __launch_bounds__(256, 2) void attn_f32_mfma_b_kernel(const float* __
       for (int kt = 0; kt < NKT; ++kt) {
         if (kt * 32 >= S) continue;
 #pragma unroll
-        for (int st = 0; st < 16; ++st)
-          o = __builtin_amdgcn_mfma_f32_32x32x2f32(sc[kt][st], dt ? v1[kt][st] : v0[kt][st], o, 0, 0, 0);
+        for (int st = 0; st < 16; ++st) o = __builtin_amdgcn_mfma_f32_32x32x2f32(sc[kt][st], vv[dt][kt][st], o, 0, 0, 0);
       }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qr = q0 + rho(r);
-        const float iv = __shfl(inv, rho(r), 64);   // 1 / l of query rho(r) (held by lane rho(r))
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[r] * iv), rout, (uint32_t)((qr * W + j) * 4),
-                                              (head * 64 + 32 * dt) * 4, 0);
-      }
+      store_o32(w, o, inv, q0, qcol + 32 * dt);
     }
   }
 }
+#endif  // MICLIP_AB
 
 // The fp32 tower's S <= 64 attention on the f16 MFMA over split operands (round 6; VERDICT r5 item
 // 5): the operands of both products are split as the tower GEMMs' are (split2h: x s = x1 + x2 + r,
@@ -660,8 +712,6 @@ __global__ __launch_bounds__(256, 2) void attn_f32_mfma_b_kernel(const float* __
 typedef _Float16 f16x8_s __attribute__((ext_vector_type(8)));
 typedef float f32x2_s __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2_s __attribute__((ext_vector_type(2)));
-
-typedef unsigned int u32x4_s __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void split8_s(const float* v, float s, f16x8_s& hi, f16x8_s& lo) {
   u32x4_s a4, b4;
@@ -686,78 +736,54 @@ __device__ __forceinline__ void split8_s(const float* v, float s, f16x8_s& hi, f
 // the weight constants api.cpp computes at load), maximised over the sequence's rows and padded by
 // 2^-8 for the rounding of the computed values; every head's wave derives the same power of two.
 // A loose bound only lowers the split's subnormal floor (|o s| < 2^14 always), as EPI_SPLIT_GELU's.
-template <int OUT, bool LATE = false>
+template <int OUT>
 __global__ __launch_bounds__(256, 2) void attn_f32s_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                           int nseq, int S, int W, int causal,
                                                           const float* __restrict__ rmax, float bw, float bb,
                                                           uint16_t* __restrict__ a3, float* __restrict__ rsc) {
   constexpr int NKT = 2;
   const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-  const int H = W / 64;
-  const int item = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform)
+  const int H = W / 64, item = wave_item();
   if (item >= nseq * H) return;
-  const int qend = (causal & ATT_Q0_ONLY) ? min(S, 32) : S;   // (ATT_Q0_ONLY: the first query block only)
+  // (attn_wave written out: profiles/precise_attn_isa.log)
+  const int qend = (causal & ATT_Q0_ONLY) ? min(S, 32) : S;
   causal &= ATT_CAUSAL;
   const int bseq = item / H, head = item % H;
   const int ld = 3 * W;
-  auto rho = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(qkv + (int64_t)bseq * S * ld), (short)0, S * ld * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(out + (int64_t)bseq * S * W), (short)0, OUT == 0 ? S * W * 4 : 0, 0x00020000);
+  const AttnWave w = {j, h, S, W, ld, bseq, head, qend, causal, make_rsrc(qkv + (int64_t)bseq * S * ld, S * ld * 4),
+                      make_rsrc(out + (int64_t)bseq * S * W, OUT == 0 ? S * W * 4 : 0)};
+  auto rho = [&](int r) { return c_row(r, h); };
   // OUT 1 / 2: the sequence's rows of the split operand, and their scale (see above)
-  const __amdgpu_buffer_rsrc_t rsp = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a3 + (OUT == 0 ? 0 : (int64_t)bseq * S * (OUT == 2 ? 2 : 3) * W)), (short)0,
-      OUT == 0 ? 0 : S * (OUT == 2 ? 2 : 3) * W * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsp = make_rsrc(a3 + (OUT == 0 ? 0 : (int64_t)bseq * S * (OUT == 2 ? 2 : 3) * W),
+                                               OUT == 0 ? 0 : S * (OUT == 2 ? 2 : 3) * W * 2);
   // (the bound first: placed after the K / V loads it measured slower, 1737 vs 1578 us at 10k
-  // frames, profiles/r06_za_bench.json)
-  // (LATE, A/B MICLIP_F32_ATTN_LATE=1: the row-max load issued first and reduced where the first
-  // query block's outputs are split, off the path to the K / V loads -- measured slower, 1537 vs
-  // 1427 us at 10k frames, profiles/r06_ze_attn_split_micro.log: it holds 7 more registers)
-  float so = 1.0f, rm = 0.f;
-  auto bound_scale = [&]() {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) rm = fmaxf(rm, __shfl_xor(rm, o, 64));
+  // frames, profiles/r06_za_bench.json; its row-max load issued first and reduced where the first
+  // query block's outputs are split measured slower too, 1537 vs 1427 us,
+  // profiles/r06_ze_attn_split_micro.log: it holds 7 more registers)
+  float so = 1.0f;
+  if constexpr (OUT != 0) {
+    const float rm = wave_max(lane < S ? rmax[(int64_t)bseq * S + lane] : 0.f);
     const float bound = (rm * bw + bb) * (1.0f + 1.0f / 256.0f);
     const int eo = __builtin_amdgcn_readfirstlane(split_exp(bound));
     so = ldexpf(1.0f, eo);
     if (head == 0 && lane < S) rsc[(int64_t)bseq * S + lane] = ldexpf(1.0f, -eo);
-  };
-  if constexpr (OUT != 0) {
-    rm = lane < S ? rmax[(int64_t)bseq * S + lane] : 0.f;
-    if constexpr (!LATE) bound_scale();
   }
-  typedef unsigned int u32x4a __attribute__((ext_vector_type(4)));
-  auto ld_row32 = [&](int r, int cb, float* v) {   // row r, columns cb + 32 h .. + 31 (rows >= S: zeros)
-    const uint32_t vo = (uint32_t)((r * ld + 32 * h) * 4);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const u32x4a t = __builtin_bit_cast(u32x4a, __builtin_amdgcn_raw_buffer_load_b128(rin, vo + 16 * c, cb * 4, 0));
-      v[4 * c] = __uint_as_float(t[0]); v[4 * c + 1] = __uint_as_float(t[1]);
-      v[4 * c + 2] = __uint_as_float(t[2]); v[4 * c + 3] = __uint_as_float(t[3]);
-    }
-  };
   // K of both key tiles and V of both dim tiles, once per (sequence, head)
   float kf[NKT][32], vf[2][NKT][16];
 #pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) ld_row32(kt * 32 + j, W + head * 64, kf[kt]);
+  for (int kt = 0; kt < NKT; ++kt) ld_row32(w, kt * 32 + j, W + head * 64, kf[kt]);
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
-      for (int st = 0; st < 16; ++st) {
-        const int key = kt * 32 + (st & 3) + 8 * (st >> 2) + 4 * h;
-        vf[dt][kt][st] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-            rin, (uint32_t)((key * ld + j) * 4), (2 * W + head * 64 + 32 * dt) * 4, 0));
-      }
+      for (int st = 0; st < 16; ++st) vf[dt][kt][st] = ld_v(w, kt, st, 2 * W + head * 64 + 32 * dt);
   float km = 0.f;
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
     for (int i = 0; i < 32; ++i) km = fmaxf(km, fabsf(kf[kt][i]));
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) km = fmaxf(km, __shfl_xor(km, o, 64));
+  km = wave_max(km);
   const int ek = __builtin_amdgcn_readfirstlane(split_exp(km));
   const float sk = ldexpf(1.0f, ek), isk = ldexpf(1.0f, -ek);
   f16x8_s k1[NKT][4], k2[NKT][4];
@@ -783,10 +809,10 @@ __global__ __launch_bounds__(256, 2) void attn_f32s_kernel(const float* __restri
 #pragma unroll
       for (int u = 0; u < 2; ++u) split8_s(&vf[dt][kt][8 * u], sv, v1[dt][kt][u], v2[dt][kt][u]);
   }
-  for (int q0 = 0; q0 < qend; q0 += 32) {
+  for (int q0 = 0; q0 < w.qend; q0 += 32) {
     const int qi = q0 + j;   // this lane's query in the S^T layout
     float qv[32];
-    ld_row32(qi, head * 64, qv);
+    ld_row32(w, qi, head * 64, qv);
     float qm = 0.f;
 #pragma unroll
     for (int i = 0; i < 32; ++i) qm = fmaxf(qm, fabsf(qv[i]));
@@ -808,6 +834,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32s_kernel(const float* __restri
         sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(k2[kt][c], q1[c], sc[kt], 0, 0, 0);
       }
     }
+    // (softmax_keys written out, with the scales undone first: profiles/precise_attn_isa.log)
     float m = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
@@ -815,7 +842,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32s_kernel(const float* __restri
       for (int r = 0; r < 16; ++r) {
         const int key = kt * 32 + rho(r);
         sc[kt][r] = (sc[kt][r] * isk) * isq8;
-        if (key >= S || (causal && key > qi)) sc[kt][r] = -INFINITY;
+        if (key >= S || (w.causal && key > qi)) sc[kt][r] = -INFINITY;
         m = fmaxf(m, sc[kt][r]);
       }
     m = fmaxf(m, __shfl_xor(m, 32, 64));
@@ -840,7 +867,6 @@ __global__ __launch_bounds__(256, 2) void attn_f32s_kernel(const float* __restri
         for (int t = 0; t < 8; ++t) pv[t] = sc[kt][8 * u + t];
         split8_s(pv, 16384.0f, p1[kt][u], p2[kt][u]);
       }
-    if constexpr (OUT != 0 && LATE) if (q0 == 0) bound_scale();
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) {
       f32x16 o = f32x16{};
@@ -857,10 +883,10 @@ __global__ __launch_bounds__(256, 2) void attn_f32s_kernel(const float* __restri
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int qr = q0 + rho(r);
-        const float iv = __shfl(inv, rho(r), 64);   // 1 / l of query rho(r) (held by lane rho(r))
+        const float iv = __shfl(inv, rho(r), 64);   // 1 / l of query rho(r), as store_o32
         const float y = (o[r] * isv[dt]) * iv;
         if constexpr (OUT == 0) {
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y), rout, (uint32_t)((qr * W + j) * 4),
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y), w.rout, (uint32_t)((qr * W + j) * 4),
                                                 (head * 64 + 32 * dt) * 4, 0);
         } else {
           // split2h's arithmetic; lanes j, j ^ 1 (dims d, d ^ 1 of row qr) pair their halves into
@@ -884,121 +910,6 @@ __global__ __launch_bounds__(256, 2) void attn_f32s_kernel(const float* __restri
     }
   }
 }
-
-// The same kernel for S <= 64 (B/32's 50 tokens: the fp32 tower's attention) with every load of a
-// (sequence, head) issued before its first MFMA (round 6).  attn_f32_mfma_kernel loads K and V
-// inside its query-block loop (twice at S > 32), each key tile's K and each (dim tile, key tile)'s
-// V as a batch that the next MFMAs wait for, and at 254 VGPRs hipcc reuses the load destinations,
-// so the Q loads went out one at a time (a load, then vmcnt(0)): ~7 serialized HBM round trips per
-// wave.  Here K and V of both key tiles (64 + 64 VGPRs) and the first query block's Q are in flight
-// together, once per (sequence, head); the second block's Q goes out behind the first block's
-// scores.  The MFMAs, their order, the masks, expf and the stores are attn_f32_mfma_kernel's, so
-// the output is bit-identical (tests/test_gpu_ops.py::test_attention_f32_prefetch_bit_identical).
-// Measured slower (scripts/attn_f32_micro.py, 10k B/32 frames: 2754 vs 2365 us,
-// profiles/r06_n_attn_f32_micro.log): at 350 VGPRs one wave per SIMD, and nothing overlaps a
-// wave's loads with another's MFMAs.  A/B only (MICLIP_ATTN_F32_V=3).
-#if MICLIP_AB
-template <int MINB>
-__global__ __launch_bounds__(256, MINB) void attn_f32_mfma_pre_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                                int nseq, int S, int W, int causal) {
-  constexpr int NKT = 2;
-  const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-  const int H = W / 64;
-  const int item = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: SGPR descriptors)
-  if (item >= nseq * H) return;
-  const int qend = (causal & ATT_Q0_ONLY) ? min(S, 32) : S;   // (ATT_Q0_ONLY: the first query block only)
-  causal &= ATT_CAUSAL;
-  const int bseq = item / H, head = item % H;
-  const int ld = 3 * W;
-  auto rho = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(qkv + (int64_t)bseq * S * ld), (short)0, S * ld * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(out + (int64_t)bseq * S * W), (short)0, S * W * 4, 0x00020000);
-  typedef unsigned int u32x4a __attribute__((ext_vector_type(4)));
-  auto ld4 = [&](int r, int col) {   // rows >= S are out of the descriptor's range: zeros
-    const u32x4a t = __builtin_bit_cast(u32x4a, __builtin_amdgcn_raw_buffer_load_b128(rin, (uint32_t)((r * ld + col) * 4), 0, 0));
-    return make_float4(__uint_as_float(t[0]), __uint_as_float(t[1]), __uint_as_float(t[2]), __uint_as_float(t[3]));
-  };
-  auto ld1 = [&](int r, int col) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rin, (uint32_t)((r * ld + col) * 4), 0, 0)); };
-  auto load_q = [&](int q0, float (&qv)[32]) {   // (rows past S: zeros)
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const float4 t = ld4(q0 + j, head * 64 + 32 * h + 4 * c);
-      qv[4 * c] = t.x * 0.125f; qv[4 * c + 1] = t.y * 0.125f; qv[4 * c + 2] = t.z * 0.125f; qv[4 * c + 3] = t.w * 0.125f;
-    }
-  };
-  // every load of the item, ahead of the first MFMA: Q of block 0, K and V of both key tiles
-  float qv[32], kv[NKT][32], vv[2][NKT][16];
-  load_q(0, qv);
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const float4 t = ld4(kt * 32 + j, W + head * 64 + 32 * h + 4 * c);
-      kv[kt][4 * c] = t.x; kv[kt][4 * c + 1] = t.y; kv[kt][4 * c + 2] = t.z; kv[kt][4 * c + 3] = t.w;
-    }
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int st = 0; st < 16; ++st) {
-        const int key = kt * 32 + (st & 3) + 8 * (st >> 2) + 4 * h;
-        vv[dt][kt][st] = ld1(key, 2 * W + head * 64 + 32 * dt + j);
-      }
-  for (int q0 = 0; q0 < qend; q0 += 32) {
-    const int qi = q0 + j;   // this lane's query in the S^T layout
-    if (q0) load_q(q0, qv);
-    f32x16 sc[NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      sc[kt] = f32x16{};
-      if (kt * 32 >= S) continue;
-#pragma unroll
-      for (int st = 0; st < 32; ++st) sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[kt][st], qv[st], sc[kt], 0, 0, 0);
-    }
-    float m = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = kt * 32 + rho(r);
-        if (key >= S || (causal && key > qi)) sc[kt][r] = -INFINITY;
-        m = fmaxf(m, sc[kt][r]);
-      }
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float l = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p = expf(sc[kt][r] - m);   // masked keys: exp(-inf) = 0
-        sc[kt][r] = p;
-        l += p;
-      }
-    l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) {
-      f32x16 o = f32x16{};
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) {
-        if (kt * 32 >= S) continue;
-#pragma unroll
-        for (int st = 0; st < 16; ++st) o = __builtin_amdgcn_mfma_f32_32x32x2f32(sc[kt][st], vv[dt][kt][st], o, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qr = q0 + rho(r);
-        const float iv = __shfl(inv, rho(r), 64);   // 1 / l of query rho(r) (held by lane rho(r))
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[r] * iv), rout, (uint32_t)((qr * W + head * 64 + 32 * dt + j) * 4), 0, 0);
-      }
-    }
-  }
-}
-
-#endif  // MICLIP_AB
 
 // ------------------------------------------------------------------ im2col + split
 // conv1's split-f16 operand straight from the pixels (P % 4 == 0, Kp = 3 P^2; B/32, B/16): one
@@ -1073,22 +984,11 @@ hipError_t gemm_f32(const float* A, int64_t lda, const float* W, int64_t ldw, co
                     int64_t ldo, int M, int N, int K, int epi, hipStream_t s, int group, int gstride, int goffset) {
   if (M <= 0 || N <= 0) return hipSuccess;
   if (K <= 0 || K % GK || lda % 4 || ldw % 4) return hipErrorInvalidValue;
-  const dim3 grid((N + GT - 1) / GT, (M + GT - 1) / GT), block(256);
-  if (epi == EPI_F32)
-    hipLaunchKernelGGL(gemm_f32_kernel<EPI_F32>, grid, block, 0, s, A, lda, W, ldw, bias, out, ldo, M, N, K, group,
-                       gstride, goffset);
-  else if (epi == EPI_GELU_BF16)
-    hipLaunchKernelGGL(gemm_f32_kernel<EPI_GELU_BF16>, grid, block, 0, s, A, lda, W, ldw, bias, out, ldo, M, N, K,
-                       group, gstride, goffset);
-  else if (epi == EPI_RELU_F32)
-    hipLaunchKernelGGL(gemm_f32_kernel<EPI_RELU_F32>, grid, block, 0, s, A, lda, W, ldw, bias, out, ldo, M, N, K,
-                       group, gstride, goffset);
-  else if (epi == EPI_RESID_F32)
-    hipLaunchKernelGGL(gemm_f32_kernel<EPI_RESID_F32>, grid, block, 0, s, A, lda, W, ldw, bias, out, ldo, M, N, K,
-                       group, gstride, goffset);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  const dim3 grid((N + GT - 1) / GT, (M + GT - 1) / GT);
+  return with_value<EPI_F32, EPI_GELU_BF16, EPI_RELU_F32, EPI_RESID_F32>(epi, [&](auto e) {
+    return launch_kernel(gemm_f32_kernel<decltype(e)::value>, grid, 256, s, A, lda, W, ldw, bias, out, ldo, M, N, K, group,
+                         gstride, goffset);
+  });
 }
 
 hipError_t split6_rows(const float* x, int64_t ldx, int64_t rows, int K, int role, int gelu, uint16_t* out,
@@ -1096,94 +996,71 @@ hipError_t split6_rows(const float* x, int64_t ldx, int64_t rows, int K, int rol
   if (rows <= 0) return hipSuccess;
   if (K % 4 || ldx % 4 || K < 4) return hipErrorInvalidValue;
   const int64_t n = rows * (K / 4);
-  hipLaunchKernelGGL(split6_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, rows, K, role, gelu, out);
-  return hipGetLastError();
+  return launch_kernel(split6_kernel, (unsigned)((n + 255) / 256), 256, s, x, ldx, rows, K, role, gelu, out);
 }
+
+// NV of the one-wave-per-row split kernels (a lane's float4s of a row of K values: K <= 256 NV)
+static int split_nv(int K) { return K <= 1024 ? 4 : K <= 3072 ? 12 : 16; }
 
 hipError_t split2h_rows(const float* x, int64_t ldx, int64_t rows, int K, int role, int gelu, uint16_t* out,
                         float* sc, hipStream_t s) {
   if (rows <= 0) return hipSuccess;
   if (K % 4 || ldx % 4 || K < 4 || K > 4096 || !sc) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  _Float16* o = (_Float16*)out;
-  if (K <= 1024) hipLaunchKernelGGL(split2h_kernel<4>, grid, dim3(256), 0, s, x, ldx, rows, K, role, gelu, o, sc);
-  else if (K <= 3072) hipLaunchKernelGGL(split2h_kernel<12>, grid, dim3(256), 0, s, x, ldx, rows, K, role, gelu, o, sc);
-  else hipLaunchKernelGGL(split2h_kernel<16>, grid, dim3(256), 0, s, x, ldx, rows, K, role, gelu, o, sc);
-  return hipGetLastError();
+  return with_value<4, 12, 16>(split_nv(K), [&](auto nv) {
+    return launch_kernel(split2h_kernel<decltype(nv)::value>, (unsigned)((rows + 3) / 4), 256, s, x, ldx, rows, K, role, gelu,
+                         (_Float16*)out, sc);
+  });
 }
 
 hipError_t layernorm_split2h(const float* x, int64_t in_stride, const float* g, const float* b, int rows, int W,
                              uint16_t* out, float* sc, hipStream_t s, float* rmax, int dup) {
   if (rows <= 0) return hipSuccess;
   if (W > 1024 || W < 4 || W % 4 || in_stride % 4) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(ln_split2h_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, in_stride, g, b, rows, W,
-                     (_Float16*)out, sc, rmax, dup ? 1 : 0);
-  return hipGetLastError();
+  return launch_kernel(ln_split2h_kernel, (rows + 3) / 4, 256, s, x, in_stride, g, b, rows, W, (_Float16*)out, sc, rmax,
+                       dup ? 1 : 0);
 }
 
 hipError_t layernorm_f32(const float* x, int64_t in_stride, const float* g, const float* b, float* out,
                          int64_t out_stride, int rows, int W, hipStream_t s, const int32_t* tokens, int S) {
   if (rows <= 0) return hipSuccess;
   if (W > 1024 || W < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(ln_f32_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, in_stride, g, b, out, out_stride, rows,
-                     W, tokens, S);
-  return hipGetLastError();
+  return launch_kernel(ln_f32_kernel, (rows + 3) / 4, 256, s, x, in_stride, g, b, out, out_stride, rows, W, tokens, S);
 }
 
-// the MFMA attention (S <= 128) is the default; MICLIP_ATTN_F32_MFMA=0 (A/B build) keeps the
-// scalar kernel for comparison
-static bool attn_f32_mfma_on() {
-#if MICLIP_AB
-  const char* e = std::getenv("MICLIP_ATTN_F32_MFMA");
-  if (e) return std::atoi(e) != 0;
-#endif
-  return true;
-}
-static int attn_f32_variant() {
-#if MICLIP_AB
-  const char* e = std::getenv("MICLIP_ATTN_F32_V");
-  if (e) return std::atoi(e);
-#endif
-  return 0;
-}
-
+// S <= 64: the split-f16 kernel; 64 < S <= 128: the exact-f32 MFMA kernel on 3 / 4 key tiles; above:
+// the scalar kernel.  The A/B build's MICLIP_ATTN_F32_V selects the other exact-f32 forms (all bit-identical):
+// 4 the batched-load kernel and 2 the general kernel on 2 key tiles, both at S <= 64; 1 the general
+// kernel with conditional loads / stores for every S <= 128.
 hipError_t attention_f32(const float* qkv, float* out, int B, int S, int W, int causal, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (W % 64 || S < 1) return hipErrorInvalidValue;
-  const int cq = causal;   // (with ATT_Q0_ONLY: the first query block only, MFMA kernels; the scalar kernels compute all)
+  // flags: with ATT_Q0_ONLY the descriptor-form MFMA kernels compute the first query block only; the
+  // scalar kernel and variant 1 take the causal bit alone and compute every row
+  const int flags = causal;
   causal &= ATT_CAUSAL;
-  const dim3 grid((unsigned)B * (W / 64));
+  if (S > 128) return launch_kernel(attn_f32_kernel, (unsigned)B * (W / 64), 256, s, qkv, out, S, W, causal);
   const dim3 grid4((unsigned)(((int64_t)B * (W / 64) + 3) / 4));
+  const int nkt = S <= 64 ? 2 : (S + 31) / 32;   // key tiles
 #if MICLIP_AB
-  if (attn_f32_mfma_on() && attn_f32_variant() == 1 && S <= 128) {   // 1: conditional loads / stores (A/B)
-    if (S <= 64) hipLaunchKernelGGL((attn_f32_mfma_kernel<2, 1, false>), grid4, dim3(256), 0, s, qkv, out, B, S, W, causal);
-    else if (S <= 96) hipLaunchKernelGGL((attn_f32_mfma_kernel<3, 1, false>), grid4, dim3(256), 0, s, qkv, out, B, S, W, causal);
-    else hipLaunchKernelGGL((attn_f32_mfma_kernel<4, 1, false>), grid4, dim3(256), 0, s, qkv, out, B, S, W, causal);
-    return hipGetLastError();
+  switch (ab_env_int("MICLIP_ATTN_F32_V", 0)) {
+    case 1:
+      return with_value<2, 3, 4>(nkt, [&](auto n) {
+        return launch_kernel(attn_f32_mfma_kernel<decltype(n)::value, 1, false>, grid4, 256, s, qkv, out, B, S, W, causal);
+      });
+    case 4:
+      if (S <= 64) return launch_kernel(attn_f32_mfma_b_kernel, grid4, 256, s, qkv, out, B, S, W, flags);
+      break;
+    case 2:   // (held to 256 registers: two waves per SIMD)
+      if (S <= 64) return launch_kernel(attn_f32_mfma_kernel<2, 2>, grid4, 256, s, qkv, out, B, S, W, flags);
+      break;
+    default: break;
   }
 #endif
-#if MICLIP_AB   // 3: every load ahead of the first MFMA (attn_f32_mfma_pre_kernel; measured slower)
-  if (attn_f32_mfma_on() && S <= 64 && attn_f32_variant() == 3) {
-    hipLaunchKernelGGL((attn_f32_mfma_pre_kernel<1>), grid4, dim3(256), 0, s, qkv, out, B, S, W, cq);
-    return hipGetLastError();
-  }
-#endif
-  if (attn_f32_mfma_on() && S <= 64 && attn_f32_variant() == 0)   // split-f16 operands (round 6)
-    hipLaunchKernelGGL(attn_f32s_kernel<0>, grid4, dim3(256), 0, s, qkv, out, B, S, W, cq, nullptr, 0.f, 0.f,
-                       nullptr, nullptr);
-  else if (attn_f32_mfma_on() && S <= 64 && attn_f32_variant() == 4)   // exact f32, batched loads (A/B)
-    hipLaunchKernelGGL(attn_f32_mfma_b_kernel, grid4, dim3(256), 0, s, qkv, out, B, S, W, cq);
-  else if (attn_f32_mfma_on() && S <= 64)   // (A/B MICLIP_ATTN_F32_V=2; held to 256 registers: two waves per SIMD)
-    hipLaunchKernelGGL((attn_f32_mfma_kernel<2, 2>), grid4, dim3(256), 0, s, qkv, out, B, S, W, cq);
-  else if (attn_f32_mfma_on() && S <= 96)
-    hipLaunchKernelGGL(attn_f32_mfma_kernel<3>, grid4, dim3(256), 0, s, qkv, out, B, S, W, cq);
-  else if (attn_f32_mfma_on() && S <= 128)
-    hipLaunchKernelGGL(attn_f32_mfma_kernel<4>, grid4, dim3(256), 0, s, qkv, out, B, S, W, cq);
-  else if (S <= 64)
-    hipLaunchKernelGGL(attn_f32_kernel<64>, grid, dim3(64), 0, s, qkv, out, S, W, causal);
-  else
-    hipLaunchKernelGGL(attn_f32_kernel<256>, grid, dim3(256), 0, s, qkv, out, S, W, causal);
-  return hipGetLastError();
+  if (S <= 64)
+    return launch_kernel(attn_f32s_kernel<0>, grid4, 256, s, qkv, out, B, S, W, flags, nullptr, 0.f, 0.f, nullptr, nullptr);
+  return with_value<3, 4>(nkt, [&](auto n) {
+    return launch_kernel(attn_f32_mfma_kernel<decltype(n)::value>, grid4, 256, s, qkv, out, B, S, W, flags);
+  });
 }
 
 hipError_t attention_f32_split(const float* qkv, const float* rmax, float bw, float bb, uint16_t* a3, int role,
@@ -1191,18 +1068,8 @@ hipError_t attention_f32_split(const float* qkv, const float* rmax, float bw, fl
   if (B <= 0) return hipSuccess;
   if (W % 64 || S < 1 || S > 64 || (role != 0 && role != 2)) return hipErrorInvalidValue;
   const dim3 grid4((unsigned)(((int64_t)B * (W / 64) + 3) / 4));
-#if MICLIP_AB
-  if (const char* le = std::getenv("MICLIP_F32_ATTN_LATE"); le && std::atoi(le) && role == 2) {
-    hipLaunchKernelGGL((attn_f32s_kernel<2, true>), grid4, dim3(256), 0, s, qkv, nullptr, B, S, W, causal, rmax, bw, bb,
-                       a3, rsc);
-    return hipGetLastError();
-  }
-#endif
-  if (role == 2)
-    hipLaunchKernelGGL(attn_f32s_kernel<2>, grid4, dim3(256), 0, s, qkv, nullptr, B, S, W, causal, rmax, bw, bb, a3, rsc);
-  else
-    hipLaunchKernelGGL(attn_f32s_kernel<1>, grid4, dim3(256), 0, s, qkv, nullptr, B, S, W, causal, rmax, bw, bb, a3, rsc);
-  return hipGetLastError();
+  auto go = [&](auto kernel) { return launch_kernel(kernel, grid4, 256, s, qkv, nullptr, B, S, W, causal, rmax, bw, bb, a3, rsc); };
+  return role == 2 ? go(attn_f32s_kernel<2>) : go(attn_f32s_kernel<1>);
 }
 
 hipError_t im2col_split2h(const void* pixels, int in_bf16, int B, int R, int P, int Kp, uint16_t* out, float* sc,
@@ -1212,21 +1079,17 @@ hipError_t im2col_split2h(const void* pixels, int in_bf16, int B, int R, int P, 
   if (rows <= 0) return hipSuccess;
   // float4 / 4 x bf16 loads of one image row: P % 4 == 0 (and R % 4 == 0 for their alignment), Kp = 3 P^2 <= 4096
   if (P % 4 || R % 4 || Kp != 3 * P * P || Kp > 4096 || !sc) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  _Float16* o = (_Float16*)out;
-  if (Kp <= 1024) hipLaunchKernelGGL(im2col_split2h_kernel<4>, grid, dim3(256), 0, s, pixels, in_bf16, rows, R, P, G, Kp, o, sc);
-  else if (Kp <= 3072) hipLaunchKernelGGL(im2col_split2h_kernel<12>, grid, dim3(256), 0, s, pixels, in_bf16, rows, R, P, G, Kp, o, sc);
-  else hipLaunchKernelGGL(im2col_split2h_kernel<16>, grid, dim3(256), 0, s, pixels, in_bf16, rows, R, P, G, Kp, o, sc);
-  return hipGetLastError();
+  return with_value<4, 12, 16>(split_nv(Kp), [&](auto nv) {
+    return launch_kernel(im2col_split2h_kernel<decltype(nv)::value>, (unsigned)((rows + 3) / 4), 256, s, pixels, in_bf16, rows,
+                         R, P, G, Kp, (_Float16*)out, sc);
+  });
 }
 
 hipError_t im2col_f32(const void* pixels, int in_bf16, float* out, int B, int R, int P, int Kp, hipStream_t s) {
   const int G = R / P;
   const int64_t total = (int64_t)B * G * G * Kp;
   if (total <= 0) return hipSuccess;
-  hipLaunchKernelGGL(im2col_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, pixels, in_bf16, out,
-                     total, R, P, G, Kp);
-  return hipGetLastError();
+  return launch_kernel(im2col_f32_kernel, (unsigned)((total + 255) / 256), 256, s, pixels, in_bf16, out, total, R, P, G, Kp);
 }
 
 }  // namespace miclip

@@ -1,6 +1,6 @@
 // Device helpers shared by every rank kernel (rank.hip, rank_filter.hip,
 // rank_mirror.hip, rank_cert.hip): order keys, the row-norm reciprocal, the
-// MFMA C-fragment row map, the data-independent bitonic top-16 list update
+// data-independent bitonic top-16 list update
 // (see rank.hip's rank_stream comment) and the workgroup / grid merges of the
 // per-lane lists.  The exact-f32 passes over LDS-staged queries built on these
 // are in rank_pass.hpp.
@@ -38,10 +38,6 @@ __device__ __forceinline__ float decode_key(uint32_t bk, int nan_first) {
   if ((bk == 0xFFFFFFFFu && nan_first) || (bk == 0u && !nan_first)) return __uint_as_float(0x7fc00000u);
   return __uint_as_float((bk & 0x80000000u) ? (bk & 0x7fffffffu) : ~bk);
 }
-
-// Row of a 32x32 MFMA C fragment that register rg (0..15) of a lane in half h (lane >> 5) holds;
-// the column is lane & 31.
-__device__ __forceinline__ constexpr int c_row(int rg, int h) { return (rg & 3) + 8 * (rg >> 2) + 4 * h; }
 
 template <typename I>
 __device__ __forceinline__ bool better(uint32_t ka, I ia, uint32_t kb, I ib) {

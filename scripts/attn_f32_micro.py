@@ -1,6 +1,6 @@
 """The fp32 tower's S <= 64 attention (mi_op_attention_f32) at the bench's pass (10k ViT-B/32
 frames, S = 50, W = 768): the product kernel (split-f16 operands, round 6) against the exact-f32 forms:
-batched loads (A/B MICLIP_ATTN_F32_V=4), the round-5 kernel (=2), the one-wave-per-SIMD prefetch kernel (=3), interleaved, HIP events, outputs compared.
+batched loads (A/B MICLIP_ATTN_F32_V=4) and the round-5 kernel (=2), interleaved, HIP events, outputs compared.
 usage: python scripts/attn_f32_micro.py [frames] [reps]"""
 import os
 import sys
@@ -21,16 +21,16 @@ def main():
     sp = torch.cuda.current_stream().cuda_stream
     g = torch.Generator(device=dev).manual_seed(3)
     qkv = torch.randn(B * S, 3 * W, device=dev, generator=g) * 2
-    outs = {k: torch.empty(B * S, W, device=dev) for k in ("split", "batched", "in_loop", "prefetch")}
+    outs = {k: torch.empty(B * S, W, device=dev) for k in ("split", "batched", "in_loop")}
     L = N.lib_ab()
 
     def run(k):
-        os.environ["MICLIP_ATTN_F32_V"] = {"split": "0", "batched": "4", "in_loop": "2", "prefetch": "3"}[k]
+        os.environ["MICLIP_ATTN_F32_V"] = {"split": "0", "batched": "4", "in_loop": "2"}[k]
         N.check(L.mi_op_attention_f32(qkv.data_ptr(), outs[k].data_ptr(), B, S, W, 0, sp), "attn f32")
     for k in outs:
         run(k)
     torch.cuda.synchronize()
-    same = all(torch.equal(outs["batched"].view(torch.int32), outs[k].view(torch.int32)) for k in ("in_loop", "prefetch"))
+    same = torch.equal(outs["batched"].view(torch.int32), outs["in_loop"].view(torch.int32))
     dev_max = ((outs["split"] - outs["batched"]).abs().max() / outs["batched"].abs().max()).item()
     best = {k: 1e30 for k in outs}
     for _ in range(3):

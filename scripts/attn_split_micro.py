@@ -1,7 +1,7 @@
 """The fp32 tower's S <= 64 attention writing out_proj's split operand (mi_op_attention_f32_split,
-role 2) at the bench's pass (10k ViT-B/32 frames): the product kernel against the A/B form with
-the bound's row-max load reduced late (MICLIP_F32_ATTN_LATE=1), and the f32-output kernel for
-reference; interleaved rounds, HIP events, split outputs compared byte for byte.
+role 2) at the bench's pass (10k ViT-B/32 frames): the product kernel, the A/B library's copy of it
+and the f32-output kernel for reference; interleaved rounds, HIP events, split outputs compared
+byte for byte.
 usage: python scripts/attn_split_micro.py [frames] [reps]"""
 import os
 import sys
@@ -23,7 +23,7 @@ def main():
     g = torch.Generator(device=dev).manual_seed(3)
     qkv = torch.randn(B * S, 3 * W, device=dev, generator=g) * 2
     rmax = qkv[:, 2 * W:].abs().amax(dim=1).contiguous()
-    out = {k: torch.zeros(B * S, 2 * W, dtype=torch.int16, device=dev) for k in ("prod", "late")}
+    out = {k: torch.zeros(B * S, 2 * W, dtype=torch.int16, device=dev) for k in ("prod", "ab")}
     sc = {k: torch.zeros(B * S, device=dev) for k in out}
     f32 = torch.empty(B * S, W, device=dev)
     P, A = N.lib(), N.lib_ab()
@@ -32,15 +32,14 @@ def main():
         if k == "f32":
             N.check(P.mi_op_attention_f32(qkv.data_ptr(), f32.data_ptr(), B, S, W, 0, sp), "attn")
             return
-        os.environ["MICLIP_F32_ATTN_LATE"] = "1" if k == "late" else "0"
-        L = A if k == "late" else P
+        L = A if k == "ab" else P
         N.check(L.mi_op_attention_f32_split(qkv.data_ptr(), rmax.data_ptr(), 1.0, 0.0, out[k].data_ptr(), 2,
                                            sc[k].data_ptr(), B, S, W, 0, sp), "attn split")
-    ks = ("prod", "late", "f32")
+    ks = ("prod", "ab", "f32")
     for k in ks:
         run(k)
     torch.cuda.synchronize()
-    same = torch.equal(out["prod"], out["late"]) and torch.equal(sc["prod"], sc["late"])
+    same = torch.equal(out["prod"], out["ab"]) and torch.equal(sc["prod"], sc["ab"])
     best = {k: 1e30 for k in ks}
     for _ in range(3):
         for k in ks:

@@ -841,7 +841,8 @@ def test_split2h_gemm_8phase_bit_identical(gpu, monkeypatch, M, N, K, epi):
 
 
 @pytest.mark.parametrize("B,S,W,causal", [(37, 50, 768, 0), (5, 77, 512, 1), (3, 1, 128, 0), (4, 33, 128, 1),
-                                          (6, 96, 256, 0), (2, 128, 128, 1), (9, 64, 192, 0)])
+                                          (6, 96, 256, 0), (2, 128, 128, 1), (9, 64, 192, 0),
+                                          (3, 65, 128, 1), (3, 97, 128, 0)])   # the first key of the 3rd / 4th key tile
 def test_attention_f32_descriptor_form_bit_identical(gpu, monkeypatch, B, S, W, causal):
     """The exact-f32 MFMA attention with its loads and stores through range-limited buffer
     descriptors (padding rows read zeros, their stores drop, no branches; the A/B build's
@@ -908,7 +909,8 @@ def _attn_ref(qkv, B, S, W, causal):
 
 
 @pytest.mark.parametrize("B,S,W,causal", [(37, 50, 768, 0), (5, 77, 512, 1), (3, 1, 128, 0), (4, 33, 128, 1),
-                                          (6, 96, 256, 0), (2, 128, 128, 1), (2, 257, 128, 0)])
+                                          (6, 96, 256, 0), (2, 128, 128, 1), (2, 257, 128, 0),
+                                          (3, 65, 128, 1), (3, 97, 128, 0)])   # the first key of the 3rd / 4th key tile
 def test_attention_f32_vs_float64(gpu, B, S, W, causal):
     """mi_op_attention_f32 (the fp32 tower's MHA core: the exact-f32 MFMA kernel for S <= 128,
     the per-row kernel above) against float64 within f32 rounding."""
@@ -960,9 +962,8 @@ def test_gemm_residual_lagging_group_early_epilogue_bit_identical(gpu, monkeypat
 def test_attention_f32_batched_bit_identical(gpu, monkeypatch, B, S, W, causal):
     """The exact-f32 MFMA forms of the fp32 tower's S <= 64 attention (A/B build): the batched-load
     kernel (attn_f32_mfma_b_kernel, MICLIP_ATTN_F32_V=4: each query block's loads issued together,
-    K and V once per (sequence, head)), the kernel that loads next to each first use (=2, the
-    round-5 default) and the one-wave-per-SIMD form with every load ahead of the first MFMA
-    (attn_f32_mfma_pre_kernel, =3): the same MFMAs in the same order, so the outputs are
+    K and V once per (sequence, head)) and the kernel that loads next to each first use (=2, the
+    round-5 default): the same MFMAs in the same order, so the outputs are
     bit-identical -- one and two key tiles, causal, 300 sequences, S = 1.  The product kernel
     (split-f16 operands) is checked against float64 by test_attention_f32_vs_float64 and against
     these by test_attention_f32_split_vs_exact."""
@@ -971,7 +972,7 @@ def test_attention_f32_batched_bit_identical(gpu, monkeypatch, B, S, W, causal):
     rng = np.random.default_rng(B * 1000 + S + W + causal)
     qkv = torch.from_numpy((rng.standard_normal((B * S, 3 * W)) * 2).astype(np.float32)).to(gpu)
     outs = []
-    for lib, env in ((_native.lib_ab(), "4"), (_native.lib_ab(), "2"), (_native.lib_ab(), "3")):
+    for lib, env in ((_native.lib_ab(), "4"), (_native.lib_ab(), "2")):
         monkeypatch.setenv("MICLIP_ATTN_F32_V", env)
         out = torch.full((B * S, W), float("nan"), device=gpu)
         _native.check(lib.mi_op_attention_f32(qkv.data_ptr(), out.data_ptr(), B, S, W, causal, _stream()), "attn f32")

@@ -183,6 +183,29 @@ def test_fp32_tower_last_block_on_cls_rows_bit_identical(gpu, monkeypatch):
     assert np.array_equal(got.view(np.int32), full.view(np.int32))
 
 
+@pytest.mark.parametrize("variant", ["4", "2"])
+def test_fp32_tower_last_block_on_cls_rows_exact_attention_bit_identical(gpu, monkeypatch, variant):
+    """The same with the last block's attention on the exact-f32 MFMA kernels (A/B build,
+    MICLIP_F32_ATTN_FUSED=0 and MICLIP_ATTN_F32_V=4, the batched-load kernel, or =2, the general
+    kernel): they too compute the first query block only (ATT_Q0_ONLY), and the embeddings equal
+    those of the full block (MICLIP_CLS_LAST=0) bit for bit.  256 frames in one chunk: the
+    smallest batch that takes the CLS-row path."""
+    import torch
+    from miclip import _native, config, model as M, weights
+    cfg = config.get_config("ViT-B/32")
+    sd = state_dict("ViT-B/32")
+    px = torch.from_numpy(weights.synthetic_pixels(256, cfg.image_resolution, seed=5))
+    monkeypatch.setattr(_native, "lib", _native.lib_ab)
+    monkeypatch.setenv("MICLIP_F32_ATTN_FUSED", "0")
+    monkeypatch.setenv("MICLIP_ATTN_F32_V", variant)
+    got = M.CLIP(cfg, sd, device=gpu, weights="fp32", image_chunk=256).encode_image(px).cpu().numpy()
+    monkeypatch.setenv("MICLIP_CLS_LAST", "0")
+    full = M.CLIP(cfg, sd, device=gpu, weights="fp32", image_chunk=256).encode_image(px).cpu().numpy()
+    monkeypatch.undo()
+    assert np.isfinite(got).all()
+    assert np.array_equal(got.view(np.int32), full.view(np.int32))
+
+
 @pytest.mark.parametrize("name,fname", [("ViT-L/14", "vit_l14.npz"), ("ViT-L/14@336px", "vit_l14_336px.npz")])
 def test_fp32_tower_l14_golden(gpu, name, fname):
     """L/14 (257 tokens) and L/14@336px (577 tokens: the 256-thread attention
