@@ -1423,6 +1423,45 @@ int mi_rank_topk_filtered(const void* corpus, int64_t N, int64_t D, int corpus_d
   return MI_OK;
 }
 
+size_t mi_rank_collapse_workspace_bytes(int64_t Q, int32_t P, int64_t D) {
+  (void)D;   // the conflict masks are per candidate, whatever the row width
+  if (Q < 0 || Q > 0x7fffffffll || P < 1 || P > RANK_REG_K) return 0;
+  return rank_collapse_workspace_bytes(Q, P);
+}
+
+int mi_rank_collapse(const void* corpus, int64_t N, int corpus_dtype, const void* corpus2, int64_t N2,
+                     int corpus2_dtype, int64_t D, int64_t index_base, const float* cand_scores,
+                     const int64_t* cand_index, int64_t Q, int32_t P, int32_t k, float threshold, float* out_scores,
+                     int64_t* out_index, int32_t* out_count, int32_t* out_slot, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  auto dtype_ok = [](int dt) { return dt == MI_F32 || dt == MI_BF16 || dt == MI_F16; };
+  if (N < 0 || N2 < 0 || Q < 0) return fail(MI_ERR_ARG, "mi_rank_collapse: negative size");
+  if (P < 1 || P > RANK_REG_K)
+    return fail(MI_ERR_UNSUPPORTED, "mi_rank_collapse: P must be in [1, %d] (got %d)", RANK_REG_K, P);
+  if (k < 1 || k > RANK_REG_K)
+    return fail(MI_ERR_UNSUPPORTED, "mi_rank_collapse: k must be in [1, %d] (got %d)", RANK_REG_K, k);
+  if (k > P) return fail(MI_ERR_ARG, "mi_rank_collapse: k = %d exceeds the pool P = %d", k, P);
+  if (D < 32 || D % 32 || D > RANK_MAX_D)
+    return fail(MI_ERR_UNSUPPORTED, "mi_rank_collapse: D must be a multiple of 32 in [32, %d] (got %lld)", RANK_MAX_D,
+                (long long)D);
+  if (!dtype_ok(corpus_dtype)) return fail(MI_ERR_ARG, "mi_rank_collapse: bad corpus dtype");
+  if (N2 > 0 && !dtype_ok(corpus2_dtype)) return fail(MI_ERR_ARG, "mi_rank_collapse: bad corpus2 dtype");
+  if (N2 > INT64_MAX - N || Q > 0x7fffffffll)
+    return fail(MI_ERR_UNSUPPORTED, "mi_rank_collapse: sizes too large for one call");
+  if (threshold != threshold) return fail(MI_ERR_ARG, "mi_rank_collapse: threshold is NaN");
+  if (Q == 0) return MI_OK;
+  const size_t need = rank_collapse_workspace_bytes(Q, P);
+  if (!workspace || workspace_bytes < need)
+    return fail(MI_ERR_ARG, "mi_rank_collapse: workspace too small (%zu < %zu)", workspace_bytes, need);
+  if (!cand_scores || !cand_index || !out_scores || !out_index || !out_count || !out_slot || (N > 0 && !corpus) ||
+      (N2 > 0 && !corpus2))
+    return fail(MI_ERR_ARG, "mi_rank_collapse: null pointer");
+  HIP_TRY(rank_collapse(corpus, N, corpus_dtype, N2 > 0 ? corpus2 : nullptr, N2, N2 > 0 ? corpus2_dtype : 0, D,
+                        index_base, cand_scores, cand_index, Q, P, k, threshold, out_scores, out_index, out_count,
+                        out_slot, workspace, (hipStream_t)stream));
+  return MI_OK;
+}
+
 int mi_mirror_build(const void* corpus, int64_t N, int64_t D, int corpus_dtype, void* mirror, void* stream) {
   int r = check_rank_args(N, D, corpus_dtype, 1, 1, MI_NORM_L2, MI_NAN_FIRST);
   if (r) return r;

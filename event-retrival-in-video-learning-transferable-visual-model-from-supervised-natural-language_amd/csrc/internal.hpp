@@ -343,6 +343,14 @@ int64_t rank_filtered_max_rows(int k);
 hipError_t rank_topk_filtered(const void* corpus, int64_t N, int64_t D, int dt, const float* q, int64_t Q, int k,
                               int64_t base, int norm_mode, int nan_first, const uint32_t* row_mask,
                               const int64_t* query_range, float* out_s, int64_t* out_i, void* ws, hipStream_t s);
+// distinct top-k (rank_collapse.hip): the greedy collapse of a [Q, P] candidate list by the cosine of
+// the stored rows; a candidate's row comes from c0 (global index - base in [0, n0)) or c1 (in
+// [n0, n0 + n1); nullptr: no second corpus); 1 <= k <= P <= 64; ws: the candidates' conflict masks
+size_t rank_collapse_workspace_bytes(int64_t Q, int P);
+hipError_t rank_collapse(const void* c0, int64_t n0, int dt0, const void* c1, int64_t n1, int dt1, int64_t D,
+                         int64_t base, const float* cand_s, const int64_t* cand_i, int64_t Q, int P, int k,
+                         float theta, float* out_s, int64_t* out_i, int32_t* out_c, int32_t* out_slot, void* ws,
+                         hipStream_t s);
 // mirrored corpus (rank_mirror.hip): fp16 unit-row mirror + certified exact re-score, k <= 16
 constexpr int MIRROR_MAX_K = 16;
 int rank_mirror_supported(int64_t D);

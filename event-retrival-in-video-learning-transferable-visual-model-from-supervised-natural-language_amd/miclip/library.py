@@ -26,7 +26,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _native as N
-from .retrieval import merge_topk, normalize_rows_f16, pack_row_mask, rank_topk_filtered
+from .retrieval import collapse_topk, merge_topk, normalize_rows_f16, pack_row_mask, rank_topk_filtered
 
 SORT_MIN_QUERIES = 32   # above it the queries are sorted by range begin (the kernel skips per 32-query block)
 
@@ -166,7 +166,7 @@ class FrameLibrary:
                 flags[off + a] = True
         return pack_row_mask(torch.from_numpy(flags).to(self.device))
 
-    def search(self, queries, k, video=None, allow=None, nan_policy="first"):
+    def search(self, queries, k, video=None, allow=None, nan_policy="first", distinct=None, pool=None):
         """Top-k frames per query over the library.
 
         ``video``: None (all videos), one name, or a length-Q list of names / None (each
@@ -174,8 +174,22 @@ class FrameLibrary:
         array | index array of frame rows (the row mask); a video absent from the dict
         is excluded.  Returns (scores f32 [Q, k], video_index int32 [Q, k], row int64
         [Q, k]); video_index (into ``names``) and row (inside its video) are -1 and the
-        score -inf in slots beyond a query's visible frames.  1 <= k <= 64."""
+        score -inf in slots beyond a query's visible frames.  1 <= k <= 64.
+
+        ``distinct=theta``: the top-k distinct frames instead.  ``pool`` candidates (default
+        ``min(64, 3 k)``, k <= pool <= 64) are fetched through the same filtered pass and
+        merge, then collapsed at cosine >= theta over both corpora (``collapse_topk``);
+        returns (scores, video_index, row, count int32 [Q, k]), count = the pool's frames
+        collapsed into the hit, itself included (0 in unused slots)."""
         import torch
+        want = k
+        if distinct is not None:
+            pool = min(64, 3 * k) if pool is None else int(pool)
+            if not 1 <= want <= pool <= 64:
+                raise N.MiClipError(f"FrameLibrary.search: distinct needs 1 <= k <= pool <= 64 (k={want}, pool={pool})")
+            k = pool
+        elif pool is not None:
+            raise N.MiClipError("FrameLibrary.search: pool is the candidate count of a distinct search")
         q = torch.as_tensor(queries)
         q = (q if q.dim() == 2 else q.reshape(1, -1)).to(device=self.device, dtype=torch.float32)
         Q = q.shape[0]
@@ -214,5 +228,16 @@ class FrameLibrary:
             s, i = cand_s[0], cand_i[0]
         else:
             s, i = merge_topk(torch.cat(cand_s, dim=1), torch.cat(cand_i, dim=1), k, nan_policy=nan_policy)
+        if distinct is not None:
+            live = [g for g in self._groups if g.rows]
+            if not live:
+                count = torch.zeros((Q, want), dtype=torch.int32, device=self.device)
+                s, i = s[:, :want], i[:, :want]
+            else:
+                # the global index runs over the non-empty groups' corpora in this order
+                second = live[1].corpus() if len(live) > 1 else None
+                s, i, count, _ = collapse_topk(live[0].corpus(), s, i, want, distinct, corpus2=second)
+            vid, row = self.locate(i)
+            return s, vid, row, count
         vid, row = self.locate(i)
         return s, vid, row

@@ -169,6 +169,78 @@ def rank_topk_filtered(corpus, queries, k, row_mask=None, query_range=None, inde
     return out_s, out_i
 
 
+def collapse_topk(corpus, cand_scores, cand_index, k, threshold, index_base=0, corpus2=None):
+    """Distinct top-k of ranked candidate lists (``mi_rank_collapse``, csrc/rank_collapse.hip).
+
+    ``cand_scores`` f32 / ``cand_index`` int64 [Q, P] are what ``rank_topk``,
+    ``rank_topk_filtered``, ``MirroredCorpus.topk`` or ``merge_topk`` returned (index -1 =
+    empty slot), trusted as ordered; 1 <= k <= P <= 64.  Candidates are walked in order: one
+    whose cosine to an accepted hit's stored row is >= ``threshold`` joins the hit in the
+    lowest such slot; otherwise it becomes the next hit while fewer than k are accepted, and
+    is dropped after that.  Rows of index ``index_base + r``, r < N, come from ``corpus``
+    [N, D]; r in [N, N + N2) from ``corpus2`` [N2, D] (dtypes may differ); any other index is
+    an empty slot.  Zero-norm rows are similar to nothing.
+
+    Returns (scores f32 [Q, k] copied bit for bit, index int64 [Q, k], count int32 [Q, k],
+    slot int32 [Q, P]) on the device: unused hit slots are (-inf, -1, 0); ``slot[q, j]`` is
+    the hit candidate j went into, -1 for empty or dropped candidates.
+    """
+    import torch
+    if not corpus.is_cuda:
+        raise N.MiClipError("collapse_topk runs on the GPU: move the corpus to the device first")
+    c = _corpus(corpus)
+    c2 = None if corpus2 is None else _corpus(corpus2).to(c.device)
+    if c2 is not None and c2.shape[1] != c.shape[1]:
+        raise N.MiClipError(f"dimension mismatch: corpus D={c.shape[1]}, corpus2 D={c2.shape[1]}")
+    s = cand_scores.to(device=c.device, dtype=torch.float32).contiguous()
+    i = cand_index.to(device=c.device, dtype=torch.int64).contiguous()
+    if s.dim() != 2 or s.shape != i.shape:
+        raise N.MiClipError("collapse_topk: cand_scores and cand_index must both be [Q, P]")
+    Q, P = s.shape
+    D = c.shape[1]
+    if not 1 <= k <= P <= REG_K:
+        raise N.MiClipError(f"collapse_topk: needs 1 <= k <= P <= {REG_K} (k={k}, P={P})")
+    if not (32 <= D <= MAX_D and D % 32 == 0):
+        raise N.MiClipError(f"D must be a multiple of 32 in [32, {MAX_D}], got {D}")
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=c.device)
+    out_i = torch.empty((Q, k), dtype=torch.int64, device=c.device)
+    out_c = torch.empty((Q, k), dtype=torch.int32, device=c.device)
+    out_slot = torch.empty((Q, P), dtype=torch.int32, device=c.device)
+    L = N.lib()
+    nbytes = L.mi_rank_collapse_workspace_bytes(Q, P, D)
+    with torch.cuda.device(c.device):
+        ws = _workspace(c.device, nbytes)
+        N.check(L.mi_rank_collapse(c.data_ptr(), c.shape[0], N.dtype_code(c.dtype),
+                                   c2.data_ptr() if c2 is not None else None,
+                                   c2.shape[0] if c2 is not None else 0,
+                                   N.dtype_code(c2.dtype) if c2 is not None else 0,
+                                   D, int(index_base), s.data_ptr(), i.data_ptr(), Q, P, int(k), float(threshold),
+                                   out_s.data_ptr(), out_i.data_ptr(), out_c.data_ptr(), out_slot.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), N.stream_ptr(c.device)), "mi_rank_collapse")
+    return out_s, out_i, out_c, out_slot
+
+
+def rank_topk_distinct(corpus, queries, k, threshold, pool=None, **rank_kwargs):
+    """Top-k distinct rows: ``rank_topk`` for ``pool`` candidates (default ``min(64, 3 k)``, the
+    reference's ``top_k * 3`` over-fetch, clipped to the row count), then ``collapse_topk`` at
+    ``threshold``.  ``rank_kwargs`` go to ``rank_topk`` (index_base, norm, nan_policy).
+    Returns ``collapse_topk``'s (scores, index, count, slot); hit slots beyond the distinct
+    rows the pool holds are (-inf, -1, 0)."""
+    if not 1 <= k <= REG_K:
+        raise N.MiClipError(f"rank_topk_distinct: k must be in [1, {REG_K}]")
+    pool = min(REG_K, 3 * k) if pool is None else int(pool)
+    if not k <= pool <= REG_K:
+        raise N.MiClipError(f"rank_topk_distinct: pool must be in [k, {REG_K}] (got {pool})")
+    pool = max(min(pool, corpus.shape[0]), k)   # rank_topk pads to k columns only when k > N
+    s, i = rank_topk(corpus, queries, pool, **rank_kwargs)
+    if s.shape[1] < k:   # fewer rows than k: the pool is every row, padded with empty slots
+        import torch
+        pad = k - s.shape[1]
+        s = torch.cat([s, s.new_full((s.shape[0], pad), float("-inf"))], dim=1)
+        i = torch.cat([i, i.new_full((i.shape[0], pad), -1)], dim=1)
+    return collapse_topk(corpus, s, i, k, threshold, index_base=rank_kwargs.get("index_base", 0))
+
+
 def normalize_rows_f16(rows, out=None):
     """``embeddings / np.linalg.norm(embeddings, axis=-1, keepdims=True)`` for a
     float16 corpus, bit for bit as NumPy evaluates it in float16

@@ -32,7 +32,7 @@ import numpy as np
 from . import api
 from .preprocess import decode_chunk, load_frames
 from .library import FrameLibrary
-from .retrieval import MirroredCorpus, normalize_rows_f16, rank_topk
+from .retrieval import MirroredCorpus, collapse_topk, normalize_rows_f16, rank_topk
 
 # corpora from this many rows on also get an fp16 ranking mirror (scripts/mirror_micro.py:
 # 1M rows 1.6-1.9x faster than the exact pass, 125k rows slower: fixed merge/re-score cost)
@@ -352,6 +352,66 @@ class EmbeddingService:
             return [frames[i] for i in idx]
         except Exception as e:
             print(f"Error in search_top_frames_by_image: {e}")
+            return []
+
+    # ------------------------------------------------------------- distinct
+    def _rank_distinct(self, video_name, query_vec, top_k, similarity, pool, with_groups):
+        """The top-k distinct frames of one video: ``_rank`` for the pool (the mirror when it
+        applies), ``collapse_topk`` over the resident rows, then the frame mapping."""
+        import torch
+        entry = self._corpus_on_device(video_name)
+        if entry is None:
+            return None
+        corpus = entry[0]
+        k = min(int(top_k), 64, corpus.shape[0])
+        if k <= 0:
+            return []
+        pool = min(64, 3 * k) if pool is None else int(pool)
+        pool = min(max(pool, k), 64, corpus.shape[0])
+        s, idx = self._rank(entry, query_vec, pool)
+        s = torch.from_numpy(np.ascontiguousarray(s)).reshape(1, -1)
+        idx = torch.from_numpy(np.ascontiguousarray(idx)).reshape(1, -1)
+        _, hit, _, slot = collapse_topk(corpus, s, idx, k, float(similarity))
+        hit, slot = hit[0].cpu().numpy(), slot[0].cpu().numpy()
+        frames = self._frames(video_name)
+        idx = idx[0].numpy()
+        if not with_groups:
+            return [frames[i] for i in hit if i >= 0]
+        return [(frames[i], [frames[j] for j in idx[slot == s] if j != i]) for s, i in enumerate(hit) if i >= 0]
+
+    def search_top_frames_distinct(self, query, top_k, video_name=None, similarity=0.9, pool=None,
+                                   with_groups=False):
+        """``search_top_frames`` for distinct moments: the best ``pool`` frames (default
+        ``min(64, 3 top_k)``, the reference's ``top_k * 3`` over-fetch) collapsed where the
+        cosine of two stored rows is >= ``similarity``; at most ``top_k`` <= 64 frames, best
+        first, each the best-ranked of its group.  ``with_groups=True``: ``[(frame, [the
+        pool's frames collapsed into it]), ...]``.  Same caching, frame mapping and
+        swallow-to-``[]`` as ``search_top_frames``."""
+        try:
+            cache_key = f"search_distinct_{self.active_model}_{query}_{top_k}_{similarity}_{pool}_{bool(with_groups)}"
+            cached = self.cache_service.get_search_results(cache_key, video_name)
+            if cached is not None:
+                return cached
+            text_features = self.get_text_features(query, video_name)
+            out = self._rank_distinct(video_name, text_features, top_k, similarity, pool, with_groups)
+            if out is None:
+                return []
+            self.cache_service.set_search_results(cache_key, video_name, out)
+            return out
+        except Exception as e:
+            print(f"Error in search_top_frames_distinct: {e}")
+            return []
+
+    def search_top_frames_by_image_distinct(self, image_features, top_k, video_name=None, similarity=0.9, pool=None,
+                                            with_groups=False):
+        """``search_top_frames_by_image`` with the collapse of ``search_top_frames_distinct``
+        (not cached, as ``search_top_frames_by_image``)."""
+        try:
+            out = self._rank_distinct(video_name, np.asarray(image_features, dtype=np.float32).reshape(-1), top_k,
+                                      similarity, pool, with_groups)
+            return [] if out is None else out
+        except Exception as e:
+            print(f"Error in search_top_frames_by_image_distinct: {e}")
             return []
 
     # --------------------------------------------------------------- ingest

@@ -180,6 +180,47 @@ int mi_rank_topk_filtered(const void* corpus, int64_t N, int64_t D, int corpus_d
                           float* out_scores, int64_t* out_index,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* Workspace bytes mi_rank_collapse needs for (Q, P, D); 0 for P outside [1, 64]. */
+size_t mi_rank_collapse_workspace_bytes(int64_t Q, int32_t P, int64_t D);
+
+/* Distinct top-k: collapses near-duplicate frames among a ranked candidate list
+ * (the reference over-fetches top_k*3 and filters on the host,
+ * query_strategies.py:55; here the rows are in HBM).  Runs after any ranking
+ * route, on the [Q,P] lists mi_rank_topk, mi_rank_topk_filtered,
+ * mi_rank_mirror or mi_rank_merge wrote: cand_scores f32 [Q,P], cand_index
+ * int64 [Q,P] (global index, -1 = empty slot), trusted as ordered, never
+ * re-sorted or re-scored.  1 <= k <= P <= 64.
+ * sim(a, b) = dot(a,b) / (|a| |b|) of the stored rows widened exactly to f32
+ * (all three sums in f32, on the exact-f32 MFMA), whatever norm mode ranked
+ * them.  A row whose sum of squares is zero or not finite is similar to
+ * nothing (the NaN-score rows MI_NAN_FIRST puts first come through one hit
+ * each); sim >= threshold is false for NaN.
+ * Walk, per query, candidates j = 0 .. P-1, empty slots skipped; accepted hits
+ * occupy slots 0, 1, ...: j joins the accepted hit in the LOWEST slot with
+ * sim >= threshold (out_slot[j] = that slot, its count += 1); else, with fewer
+ * than k hits accepted, j becomes the next hit (count 1); else out_slot[j] =
+ * -1.  The walk runs to the end of the list; similarity is not made
+ * transitive (a~b, b~c, a!~c in that order: hits a (count 2) and c (count 1)).
+ * Rows: a candidate whose index - index_base is in [0, N) is read from corpus
+ * (corpus_dtype), one in [N, N + N2) from corpus2 (corpus2_dtype; NULL, 0, 0:
+ * one corpus); the two dtypes (MI_F32 / MI_BF16 / MI_F16) may differ, row
+ * stride D, 32 <= D <= 1024, D % 32 == 0.  Any other index is an empty slot
+ * and is never dereferenced.
+ * out_scores f32 [Q,k] (copied bit for bit from cand_scores) and out_index
+ * int64 [Q,k]: the accepted hits in order, unused slots -inf / -1; out_count
+ * int32 [Q,k]: candidates collapsed into the hit, itself included, 0 in unused
+ * slots; out_slot int32 [Q,P]: -1 for empty candidates.  workspace receives the
+ * candidates' conflict masks, uint64 [Q,P]: bit i of mask j = sim(i, j) >=
+ * threshold.  All arrays are read by the kernel: no synchronisation, capturable.
+ * Q = 0 returns MI_OK. */
+int mi_rank_collapse(const void* corpus, int64_t N, int corpus_dtype,
+                     const void* corpus2, int64_t N2, int corpus2_dtype,
+                     int64_t D, int64_t index_base,
+                     const float* cand_scores, const int64_t* cand_index, int64_t Q, int32_t P,
+                     int32_t k, float threshold,
+                     float* out_scores, int64_t* out_index, int32_t* out_count, int32_t* out_slot,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* Ranking mirror of a corpus for mi_rank_mirror (an
  * HBM-resident half-width mirror beside the f32 master of
  * EmbeddingService.get_embeddings, embedding_service.py:186-217).
