@@ -1790,19 +1790,19 @@ static int check_jpeg_args(const char* fn, const uint8_t* data, int64_t data_byt
   if (huff_idx && nsets < 1) return fail(MI_ERR_ARG, "%s: huff_idx needs nsets >= 1", fn);
   if (B == 0) return MI_OK;
   if (!data || !seg_off || !seg_end || !huff || !qtab || !out) return fail(MI_ERR_ARG, "%s: null pointer", fn);
-  const int W = geom[0], H = geom[1], nc = geom[2], ri = geom[3], nseg = geom[4];
+  const int W = geom[JG_W], H = geom[JG_H], nc = geom[JG_NCOMP], ri = geom[JG_RI], nseg = geom[JG_NSEG];
   if (W < 1 || H < 1 || W > 65535 || H > 65535 || (nc != 1 && nc != 3) || ri < 0 || nseg < 1)
     return fail(MI_ERR_ARG, "%s: bad geometry", fn);
   if (nc == 3) {
-    const int h0 = geom[5], v0 = geom[6];
+    const int h0 = geom[JG_HS], v0 = geom[JG_VS];
     const bool luma_ok = (h0 == 1 && v0 == 1) || (h0 == 2 && v0 == 1) || (h0 == 2 && v0 == 2);
     for (int c = 1; c < 3; ++c)
-      if (geom[5 + 2 * c] != 1 || geom[6 + 2 * c] != 1 || !luma_ok)
+      if (geom[JG_HS + 2 * c] != 1 || geom[JG_VS + 2 * c] != 1 || !luma_ok)
         return fail(MI_ERR_UNSUPPORTED, "%s: sampling must be luma 1x1/2x1/2x2 with chroma 1x1", fn);
   }
   for (int c = 0; c < nc; ++c)
-    if (geom[11 + c] < 0 || geom[11 + c] > 3 || geom[14 + c] < 0 || geom[14 + c] > 1 || geom[17 + c] < 0 ||
-        geom[17 + c] > 1)
+    if (geom[JG_QSEL + c] < 0 || geom[JG_QSEL + c] > 3 || geom[JG_DCSEL + c] < 0 || geom[JG_DCSEL + c] > 1 ||
+        geom[JG_ACSEL + c] < 0 || geom[JG_ACSEL + c] > 1)
       return fail(MI_ERR_ARG, "%s: bad table selector", fn);
   const size_t need = jpeg_workspace_bytes(geom, B, data_bytes);
   if (!workspace || workspace_bytes < need)
@@ -1834,9 +1834,9 @@ int mi_jpeg_decode_transform(const uint8_t* data, int64_t data_bytes, const int6
   if (B == 0) return MI_OK;
   // the fit check comes first, so no decode work is queued for a geometry the fused transform
   // cannot take; every error after it is a HIP error
-  if (!jpeg_xform_fits(geom[1], geom[0], n, mode))
+  if (!jpeg_xform_fits(geom[JG_H], geom[JG_W], n, mode))
     return fail(MI_ERR_UNSUPPORTED, "mi_jpeg_decode_transform: %dx%d -> %d does not fit one LDS band: use "
-                "mi_jpeg_decode + mi_preprocess_frames", geom[0], geom[1], n);
+                "mi_jpeg_decode + mi_preprocess_frames", geom[JG_W], geom[JG_H], n);
   const JpegXform xf{n, mode, out_dtype == MI_BF16, out};
   HIP_TRY(jpeg_decode(data, data_bytes, seg_off, seg_end, huff, huff_idx, nsets, qtab, geom, B, nullptr, workspace,
                       workspace_bytes, (hipStream_t)stream, &xf));

@@ -52,6 +52,34 @@ __device__ __host__ __forceinline__ float bf2f(u16 h) {
   return v.f;
 }
 
+// ---- Pillow / torchvision arithmetic of the frame transform: preprocess.hip's resample kernels and
+// jpeg.hip's fused transform kernel compute the same values with it
+constexpr int PRECISION_BITS = 22;   // Pillow PRECISION_BITS = 32 - 8 - 2: a resample sum's fractional bits
+__device__ __forceinline__ uint32_t clip8(int acc) {
+  acc >>= PRECISION_BITS;
+  return acc < 0 ? 0u : (acc > 255 ? 255u : (uint32_t)acc);
+}
+// torchvision's Normalize constants (CLIP mean / std) as it builds them: Python floats (double) -> float32
+inline void clip_norm(float (&mean)[3], float (&sd)[3]) {
+  const float m[3] = {(float)0.48145466, (float)0.4578275, (float)0.40821073};
+  const float s[3] = {(float)0.26862954, (float)0.26130258, (float)0.27577711};
+  for (int c = 0; c < 3; ++c) {
+    mean[c] = m[c];
+    sd[c] = s[c];
+  }
+}
+// torchvision ToTensor (x / 255) then Normalize ((x - mean) / std) of channel c's uint8 value px,
+// f32, no contraction; stored as f32 or bf16
+__device__ __forceinline__ float to_tensor_normalize(uint32_t px, const float (&mean)[3], const float (&sd)[3], int c) {
+#pragma clang fp contract(off)
+  return ((float)px / 255.0f - mean[c]) / sd[c];
+}
+template <bool OUT_BF16>
+__device__ __forceinline__ void store_out(void* __restrict__ out, int64_t o, float v) {
+  if (OUT_BF16) ((uint16_t*)out)[o] = f2bf(v);
+  else ((float*)out)[o] = v;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -57,6 +57,14 @@ inline int ab_env_int(const char* name, int fallback) {
 constexpr int ab_env_int(const char*, int fallback) { return fallback; }
 #endif
 
+// A dispatch counts its work-items in 32 bits (grid x block < 2^32), so a kernel with `per_frame`
+// work-items per frame runs over chunks of frames: the frames per launch such that a launch has at
+// most `limit` items, at least one (per_frame = 0: all nframes at once)
+inline int64_t frames_per_launch(int64_t per_frame, int64_t nframes, int64_t limit = (int64_t)1 << 31) {
+  if (per_frame <= 0) return nframes;
+  return limit / per_frame > 0 ? limit / per_frame : 1;
+}
+
 // Switches that ride in attention()'s `flags` beside the causal bit (values fixed by the C ABI:
 // mi_op_attention passes its `causal` argument through, and accepts the first three).
 enum AttnFlags {
@@ -207,6 +215,17 @@ struct JpegXform {
   void* out;
 };
 bool jpeg_xform_fits(int H, int W, int n, int mode);
+// the slots of geom[20] (include/miclip.h mi_jpeg_decode); component c's entry of a per-component
+// group is at GROUP + c, its sampling factors at JG_HS + 2 c / JG_VS + 2 c
+enum JpegGeomSlot {
+  JG_W = 0, JG_H = 1, JG_NCOMP = 2,
+  JG_RI = 3,      // restart interval in MCUs (0: none)
+  JG_NSEG = 4,    // segments (restart intervals) per frame
+  JG_HS = 5, JG_VS = 6,
+  JG_QSEL = 11,   // quantisation table (0..3)
+  JG_DCSEL = 14, JG_ACSEL = 17,   // Huffman tables (0..1)
+  JG_SLOTS = 20
+};
 hipError_t jpeg_decode(const uint8_t* data, int64_t data_bytes, const int64_t* seg_off, const int64_t* seg_end,
                        const void* huff, const int32_t* huff_idx, int nsets, const uint16_t* qtab, const int32_t* geom,
                        int nframes, uint8_t* out_rgb, void* ws, size_t ws_bytes, hipStream_t s,
@@ -399,12 +418,13 @@ int resample_coeffs(int in_size, double in0, double in1, int out_size, int filte
 size_t preprocess_workspace_bytes(int64_t B, int H, int W, int n, int mode);
 // the device coefficient tables of mi_preprocess_frames' resample (H x W -> n x n crop, mode as
 // there): horizontal kh [n][ksh] / bh [n][2], vertical kv [n][ksv] / bv [n][2] (Pillow's int32
-// coefficients and (first tap, taps)); the crop's source columns [xlo, xlo + xw); bv on the host
+// coefficients and (first tap, taps)); the source rows [r0, r0 + rows) and columns [xlo, xlo + xw)
+// that the crop's taps read
 struct ResampleTables {
   const int32_t *kh = nullptr, *bh = nullptr, *kv = nullptr, *bv = nullptr;
-  int ksh = 0, ksv = 0, xlo = 0, xw = 0;
-  std::vector<int32_t> hbv;
-  int32_t wmax = 0;   // largest |coefficient|
+  int ksh = 0, ksv = 0, r0 = 0, rows = 0, xlo = 0, xw = 0;
+  std::vector<int32_t> hbv;   // host copy of bv (the fused JPEG transform sizes its row bands from it)
+  int32_t wmax = 0;           // largest |coefficient| of kh / kv (24-bit multiplies apply below 2^23)
 };
 hipError_t resample_tables(int H, int W, int n, int mode, ResampleTables& t);
 // frames uint8 [B,H,W,3] -> out [B,3,n,n] f32 / bf16; mode 0 CLIP _transform, 1 squash (bilinear)

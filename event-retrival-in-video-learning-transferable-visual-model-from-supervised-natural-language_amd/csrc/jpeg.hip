@@ -2,21 +2,32 @@
 // the decode step of the reference's frame ingest
 //   Image.open(path).convert("RGB")        embedding_service.py:472-480, embedding.py:46
 // (SURVEY.md §8(f) item 1).  Pillow hands YCbCr JPEGs to libjpeg(-turbo) with
-// its defaults (JDCT_ISLOW, fancy upsampling, JCS_RGB output), so the three
-// kernels below restate those integer algorithms:
-//   jpeg_entropy_kernel  one lane per frame (or per restart interval):
-//                        sequential Huffman decode of the interleaved scan
-//                        (tables in LDS, stream words prefetched), DC
-//                        prediction, de-zigzag -> int16 coefficients;
-//   jpeg_idct_kernel     one thread per 8x8 block: dequantise + the
-//                        LL&M integer IDCT of jidctint.c (CONST_BITS 13,
-//                        PASS1_BITS 2) with its 1024-entry range-limit
-//                        wrap -> uint8 component planes;
-//   jpeg_color_kernel    one thread per output pixel: h2v1 / h2v2 "fancy"
-//                        triangular chroma upsampling (jdsample.c, edge rows
-//                        and columns replicated as libjpeg's context rows do)
-//                        and the fixed-point YCbCr -> RGB of jdcolor.c.
-// The host (miclip/jpeg.py) parses the headers, builds the Huffman look-up
+// its defaults (JDCT_ISLOW, fancy upsampling, JCS_RGB output), so the kernels
+// below restate those integer algorithms, in three stages:
+//   entropy   Huffman decode of the interleaved scan, DC prediction -> int16
+//             coefficients in zigzag order.  Scans with restart markers:
+//             jpeg_entropy_kernel, one lane per (frame, restart interval),
+//             tables in LDS, stream words prefetched.  Scans without: the
+//             chunked decode, a lane per 1-KB chunk (jp_layout / jp_chunk_frame,
+//             jp_unstuff_*, jp_sync rounds, jp_prefix, jp_final; see "speculative
+//             parallel entropy decode" below), then jpeg_entropy_kernel for the
+//             frames its layout leaves out.  Both share one symbol step
+//             (jp_symbol) and one table staging (jp_stage_tables);
+//   IDCT      jpeg_idct_kernel, one thread per 8x8 block: dequantise + the
+//             LL&M integer IDCT of jidctint.c (CONST_BITS 13, PASS1_BITS 2)
+//             with its 1024-entry range-limit wrap -> uint8 component planes;
+//   output    h2v1 / h2v2 "fancy" triangular chroma upsampling (jdsample.c,
+//             edge rows and columns replicated as libjpeg's context rows do)
+//             and the fixed-point YCbCr -> RGB of jdcolor.c (ycc_rgb), either
+//             as RGB frames (jpeg_color_kernel, one thread per 4 pixels) or
+//             fused with Pillow's resample, the crop and ToTensor / Normalize
+//             (jpeg_transform_kernel: mi_jpeg_decode_transform).
+// Host side, at the end of the file: jpeg_layout turns geom[] into everything
+// derived from it, jpeg_workspace lists the workspace once (sizes for
+// jpeg_workspace_bytes, pointers for jpeg_decode), and jpeg_decode is the
+// sequence of the stage functions entropy_chunked / entropy_serial,
+// idct_stage, rgb_stage / transform_stage.
+// The caller (miclip/jpeg.py) parses the headers, builds the Huffman look-up
 // tables and batches frames of one geometry; progressive / arithmetic /
 // 12-bit / CMYK / other sampling layouts stay on the host decoder.
 #include <hip/hip_runtime.h>
@@ -254,6 +265,40 @@ __device__ __forceinline__ int extend(uint32_t v, int s) {
   return (int)v < (1 << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v;
 }
 
+// The symbol step of both entropy decodes (jpeg_entropy_kernel, jp_run), after fill(): the Huffman
+// symbol of table tp split into size sz and zero run r (k = 0, the DC coefficient: the symbol is the
+// size category, <= 15, host-checked, and there is no run), then the sz extra bits as the value
+// (results through references: returned as a struct, the chunk kernels came out four instructions longer)
+template <typename BR>
+__device__ __forceinline__ void jp_symbol(BR& br, const JpegHuff* __restrict__ tp, int k, int& sz, int& r, int& val) {
+  const int sym = huff_decode(br, tp);
+  sz = sym & 15;
+  r = k ? (sym >> 4) : 0;
+  const uint32_t bits = sz ? br.peek(sz) : 0u;
+  br.skip(sz);
+  val = sz ? extend(bits, sz) : 0;
+}
+
+// The launch's table sets for the entropy kernels (NT threads).  LDS_T: the nsets <= JPEG_LDS_SETS
+// sets (nsets * 4 tables) are copied into the dynamic LDS, and the caller places the barrier before its
+// first look-up; otherwise they are read from global memory.  Returns the base of the sets;
+// jp_frame_tables picks frame f's (set huff_idx[f], or f without huff_idx) once f is known.
+template <bool LDS_T, int NT>
+__device__ __forceinline__ const JpegHuff* jp_stage_tables(const JpegHuff* huff, int nsets) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // the launch's dynamic LDS
+  if (LDS_T) {
+    const uint32_t* src = (const uint32_t*)huff;
+    uint32_t* dst = (uint32_t*)smem;
+    const int nw = nsets * 4 * (int)sizeof(JpegHuff) / 4;
+    for (int i = threadIdx.x; i < nw; i += NT) dst[i] = src[i];
+  }
+  return LDS_T ? (const JpegHuff*)smem : huff;
+}
+__device__ __forceinline__ const JpegHuff* jp_frame_tables(const JpegHuff* sets, const int32_t* huff_idx, int f) {
+  const int set = huff_idx ? huff_idx[f] : f;
+  return sets + (int64_t)set * 4;
+}
+
 // Per frame f: entropy-coded bytes at data + off[f] (len[f] bytes), tables at
 // huff[set * 4 + {dc0, ac0, dc1, ac1}] with set = huff_idx[f] (f without
 // huff_idx), coefficient output coef + f * blocks_per_frame * 64 (zeroed by the
@@ -287,14 +332,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
                                                           const int32_t* __restrict__ huff_idx, int nsets,
                                                           JpegGeom g, int nframes, int16_t* __restrict__ coef,
                                                           int64_t data_bytes, const uint8_t* __restrict__ skip) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  JpegHuff* sh = (JpegHuff*)smem;
-  if (LDS_T) {
-    const uint32_t* src = (const uint32_t*)huff;
-    uint32_t* dst = (uint32_t*)smem;
-    const int nw = nsets * 4 * (int)sizeof(JpegHuff) / 4;
-    for (int i = threadIdx.x; i < nw; i += 64) dst[i] = src[i];
-  }
+  const JpegHuff* sets = jp_stage_tables<LDS_T, 64>(huff, nsets);
   __syncthreads();
   const int64_t lane = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (lane >= (int64_t)nframes * g.nseg) return;
@@ -303,8 +341,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
   BitReader br;
   const int64_t so = min(max(seg_off[lane], (int64_t)0), data_bytes);
   br.init(data + so, data + min(max(seg_end[lane], so), data_bytes));
-  const int set = huff_idx ? huff_idx[f] : f;
-  const JpegHuff* T = (LDS_T ? (const JpegHuff*)sh : huff) + (int64_t)set * 4;
+  const JpegHuff* T = jp_frame_tables(sets, huff_idx, f);
   int16_t* out = coef + (int64_t)f * g.blocks_per_frame * 64;
   const int total = g.mcux * g.mcuy;
   int m = g.ri ? s * g.ri : 0;
@@ -325,12 +362,8 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     const JpegHuff* tp = k ? pick3(c, a0, a1, a2) : pick3(c, d0, d1, d2);
     if (__any(br.low())) br.refill();   // one wave-wide load for every lane with room
     br.fill();
-    const int sym = huff_decode(br, tp);
-    const int sz = sym & 15;   // DC: the size category (<= 15, host-checked)
-    const int r = k ? (sym >> 4) : 0;
-    const uint32_t bits = sz ? br.peek(sz) : 0u;
-    br.skip(sz);
-    const int val = sz ? extend(bits, sz) : 0;
+    int sz, r, val;
+    jp_symbol(br, tp, k, sz, r, val);
     bool endblk;
     if (k == 0) {
       const int pv = pick3(c, p0, p1, p2) + val;
@@ -533,12 +566,8 @@ __device__ __forceinline__ void jp_run(UReader& br, const JpegHuff* __restrict__
                            : T + pick3(c, g.dcsel[0], g.dcsel[1], g.dcsel[2]) * 2;
     if (__any(br.low())) br.refill();   // one wave-wide load for every lane with room
     br.fill();
-    const int sym = huff_decode(br, tp);
-    const int sz = sym & 15;
-    const int r = k ? (sym >> 4) : 0;
-    const uint32_t bits = sz ? br.peek(sz) : 0u;
-    br.skip(sz);
-    const int val = sz ? extend(bits, sz) : 0;
+    int sz, r, val;
+    jp_symbol(br, tp, k, sz, r, val);
     bool endblk;
     if (k == 0) {
       const int pv = pick3(c, dc[0], dc[1], dc[2]) + val;
@@ -822,14 +851,8 @@ __global__ __launch_bounds__(256) void jp_sync_kernel(const uint8_t* __restrict_
                                                       JpegMcu mc, int round, JpState src, JpState dst,
                                                       int32_t* __restrict__ frame_changed /* this round's [B] */,
                                                       JpCps cps) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  if (LDS_T) {
-    const uint32_t* s = (const uint32_t*)huff;
-    uint32_t* d = (uint32_t*)smem;
-    const int nw = nsets * 4 * (int)sizeof(JpegHuff) / 4;
-    for (int i = threadIdx.x; i < nw; i += 256) d[i] = s[i];
-    __syncthreads();
-  }
+  const JpegHuff* sets = jp_stage_tables<LDS_T, 256>(huff, nsets);
+  if (LDS_T) __syncthreads();
   const int64_t ci = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (ci >= nchunks_max) return;
   const int f = ch.cframe[ci];
@@ -863,8 +886,7 @@ __global__ __launch_bounds__(256) void jp_sync_kernel(const uint8_t* __restrict_
     dst.changed[ci] = 0;
     return;
   }
-  const int set = huff_idx ? huff_idx[f] : f;
-  const JpegHuff* T = (LDS_T ? (const JpegHuff*)smem : huff) + (int64_t)set * 4;
+  const JpegHuff* T = jp_frame_tables(sets, huff_idx, f);
   const uint32_t stop = (uint64_t)(t + 1) * JP_CHUNK >= L ? L * 8u : first + JP_CHUNK * 8u;
   UReader br;
   br.init_at(ustuff + ch.ubase[f], L, start);
@@ -942,14 +964,7 @@ __global__ __launch_bounds__(256) void jp_final_kernel(const uint8_t* __restrict
                                                        const int32_t* __restrict__ pred,
                                                        const int32_t* __restrict__ frame_changed,
                                                        int16_t* __restrict__ coef, int abl) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  JpegHuff* sh = (JpegHuff*)smem;
-  if (LDS_T) {
-    const uint32_t* s = (const uint32_t*)huff;
-    uint32_t* d = (uint32_t*)smem;
-    const int nw = nsets * 4 * (int)sizeof(JpegHuff) / 4;
-    for (int i = threadIdx.x; i < nw; i += 256) d[i] = s[i];
-  }
+  const JpegHuff* sets = jp_stage_tables<LDS_T, 256>(huff, nsets);
   __syncthreads();
   const int64_t ci = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (ci >= nchunks_max) return;
@@ -977,8 +992,7 @@ __global__ __launch_bounds__(256) void jp_final_kernel(const uint8_t* __restrict
   }
   const bool last = serial || (uint64_t)(t + 1) * JP_CHUNK >= L;
   const uint32_t stop = last ? 0xFFFFFFFFu : (uint32_t)(t + 1) * (JP_CHUNK * 8u);
-  const int set = huff_idx ? huff_idx[f] : f;
-  const JpegHuff* T = (LDS_T ? (const JpegHuff*)sh : huff) + (int64_t)set * 4;
+  const JpegHuff* T = jp_frame_tables(sets, huff_idx, f);
   UReader br;
   br.init_at(ustuff + ch.ubase[f], L, start);
   int nblk = 0;
@@ -1137,22 +1151,32 @@ __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ P, int ps, 
   return (th * 3 + nx + 7) >> 4;
 }
 
+// jdcolor.c's YCbCr -> RGB (cb, cr centred: sample - 128), packed R | G << 8 | B << 16.
+// FIX(x) = (int)(x * 65536 + 0.5); ONE_HALF = 1 << 15; arithmetic right shifts
+__device__ __forceinline__ uint32_t ycc_rgb(int Y, int cb, int cr) {
+  const int r = Y + ((91881 * cr + 32768) >> 16);
+  const int gch = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+  const int b = Y + ((116130 * cb + 32768) >> 16);
+  return (uint32_t)clamp255(r) | ((uint32_t)clamp255(gch) << 8) | ((uint32_t)clamp255(b) << 16);
+}
+
+// RGB of pixel (x, y) of one frame's planes
+__device__ __forceinline__ uint32_t color_xy(const uint8_t* base, const JpegPlanes& pl, int ncomp,
+                                             int cmode, int cdw, int cdh, int x, int y) {
+  const int Y = base[pl.pbase[0] + (int64_t)y * pl.pstride[0] + x];
+  if (ncomp == 1) return (uint32_t)Y * 0x010101u;
+  const int cb = chroma_at(base + pl.pbase[1], pl.pstride[1], cdw, cdh, x, y, cmode) - 128;
+  const int cr = chroma_at(base + pl.pbase[2], pl.pstride[2], cdw, cdh, x, y, cmode) - 128;
+  return ycc_rgb(Y, cb, cr);
+}
+
 // RGB of output pixel t (frame-major over nframes x W x H)
 __device__ __forceinline__ uint32_t color_px(const uint8_t* __restrict__ planes, const JpegPlanes& pl, int W,
                                              int64_t px, int ncomp, int cmode, int cdw, int cdh, int64_t t) {
   const int f = (int)(t / px);
   const int64_t p = t - (int64_t)f * px;
   const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
-  const uint8_t* base = planes + (int64_t)f * pl.plane_frame_bytes;
-  const int Y = base[pl.pbase[0] + (int64_t)y * pl.pstride[0] + x];
-  if (ncomp == 1) return (uint32_t)Y * 0x010101u;
-  const int cb = chroma_at(base + pl.pbase[1], pl.pstride[1], cdw, cdh, x, y, cmode) - 128;
-  const int cr = chroma_at(base + pl.pbase[2], pl.pstride[2], cdw, cdh, x, y, cmode) - 128;
-  // FIX(x) = (int)(x * 65536 + 0.5); ONE_HALF = 1 << 15; arithmetic right shifts
-  const int r = Y + ((91881 * cr + 32768) >> 16);
-  const int gch = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-  const int b = Y + ((116130 * cb + 32768) >> 16);
-  return (uint32_t)clamp255(r) | ((uint32_t)clamp255(gch) << 8) | ((uint32_t)clamp255(b) << 16);
+  return color_xy(planes + (int64_t)f * pl.plane_frame_bytes, pl, ncomp, cmode, cdw, cdh, x, y);
 }
 
 // one thread per 4 consecutive output pixels: 12 bytes as three dword stores
@@ -1189,33 +1213,14 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restri
 // vertically and normalises.  Every step is the same integer arithmetic as color_px and
 // preprocess.hip's resample_h / resample_v kernels, so the output is bit-identical to decode +
 // mi_preprocess_frames (and so to Pillow + torchvision).
-constexpr int XF_PREC = 22;   // Pillow PRECISION_BITS
 constexpr int XF_RPI = 8;     // source rows converted per step
 constexpr int XF_NT = 512;    // threads per workgroup (two workgroups per CU: <= XF_LDS2 bytes of LDS each)
 constexpr int XF_IPT = 3;     // 4-pixel groups per thread whose loads go out together in a conversion step
 constexpr size_t XF_LDS2 = 78 * 1024;
 
-__device__ __forceinline__ uint32_t xf_clip8(int acc) {
-  acc >>= XF_PREC;
-  return acc < 0 ? 0u : (acc > 255 ? 255u : (uint32_t)acc);
-}
-
-// RGB of pixel (x, y) of one frame's planes (color_px without the frame-major index)
-__device__ __forceinline__ uint32_t color_xy(const uint8_t* __restrict__ base, const JpegPlanes& pl, int ncomp,
-                                             int cmode, int cdw, int cdh, int x, int y) {
-  const int Y = base[pl.pbase[0] + (int64_t)y * pl.pstride[0] + x];
-  if (ncomp == 1) return (uint32_t)Y * 0x010101u;
-  const int cb = chroma_at(base + pl.pbase[1], pl.pstride[1], cdw, cdh, x, y, cmode) - 128;
-  const int cr = chroma_at(base + pl.pbase[2], pl.pstride[2], cdw, cdh, x, y, cmode) - 128;
-  const int r = Y + ((91881 * cr + 32768) >> 16);
-  const int gch = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-  const int b = Y + ((116130 * cb + 32768) >> 16);
-  return (uint32_t)clamp255(r) | ((uint32_t)clamp255(gch) << 8) | ((uint32_t)clamp255(b) << 16);
-}
-
 // RGB of the 4 pixels x0 .. x0 + 3 of row y (x0 % 4 == 0, 1 <= x0, x0 + 4 < W: no chroma edge
 // column): one dword of Y and one (unaligned) dword per chroma row instead of a byte load per
-// sample; the same fancy-upsampling / colour arithmetic as chroma_at + color_px
+// sample; the same fancy-upsampling / colour arithmetic as chroma_at + color_xy
 // 4 bytes at any address as one value: the two aligned dwords around them, byte-aligned
 __device__ __forceinline__ uint32_t load4u(const uint8_t* p) {
   const uintptr_t a = (uintptr_t)p;
@@ -1254,8 +1259,7 @@ __device__ __forceinline__ Raw4 color4_load(const uint8_t* __restrict__ base, co
 }
 
 // RGB of the 4 pixels x0 .. x0 + 3 of row y (x0 % 4 == 0, 1 <= x0, x0 + 4 < W: no chroma edge
-// column) from color4_load's words; the same fancy-upsampling / colour arithmetic as
-// chroma_at + color_px
+// column) from color4_load's words; the same fancy-upsampling arithmetic as chroma_at
 __device__ __forceinline__ void color4_math(const Raw4& w, int cmode, uint32_t* __restrict__ o) {
   int cb[4], cr[4];
   if (cmode == 0) {
@@ -1299,14 +1303,7 @@ __device__ __forceinline__ void color4_math(const Raw4& w, int cmode, uint32_t* 
     }
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int Y = (int)((w.y >> (8 * i)) & 255u);
-    const int b_ = cb[i] - 128, r_ = cr[i] - 128;
-    const int r = Y + ((91881 * r_ + 32768) >> 16);
-    const int gch = Y + ((-22554 * b_ + 32768 - 46802 * r_) >> 16);
-    const int b = Y + ((116130 * b_ + 32768) >> 16);
-    o[i] = (uint32_t)clamp255(r) | ((uint32_t)clamp255(gch) << 8) | ((uint32_t)clamp255(b) << 16);
-  }
+  for (int i = 0; i < 4; ++i) o[i] = ycc_rgb((int)((w.y >> (8 * i)) & 255u), cb[i] - 128, cr[i] - 128);
 }
 
 struct XformK {
@@ -1329,7 +1326,6 @@ template <bool OUT_BF16, bool I24>
 __global__ __launch_bounds__(XF_NT) void jpeg_transform_kernel(const uint8_t* __restrict__ planes, JpegPlanes pl,
                                                              int ncomp, int cmode, int cdw, int cdh, XformK xk,
                                                              void* __restrict__ out) {
-#pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) char xsm[];
   const int f = (int)(blockIdx.x / xk.nbands), band = (int)(blockIdx.x % xk.nbands);
   const int n = xk.n, xw = xk.xw;   // xw: the crop's source span rounded out to whole 4-pixel groups
@@ -1400,7 +1396,7 @@ __global__ __launch_bounds__(XF_NT) void jpeg_transform_kernel(const uint8_t* __
       const int bh = sbh[ox], xb = bh & 0xFFFF, xs = bh >> 16;
       const int32_t* k = skh + ox * xk.ksh;
       const uint32_t* p = crow + rr * xw + xb;
-      int s0 = 1 << (XF_PREC - 1), s1 = s0, s2 = s0;
+      int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
       for (int j = 0; j < xs; ++j) {
         const uint32_t v = p[j];
         const int w = k[j];
@@ -1408,7 +1404,7 @@ __global__ __launch_bounds__(XF_NT) void jpeg_transform_kernel(const uint8_t* __
         s1 += xf_mul<I24>((v >> 8) & 255u, w);
         s2 += xf_mul<I24>((v >> 16) & 255u, w);
       }
-      hrow[(r0 - ra + rr) * n + ox] = xf_clip8(s0) | (xf_clip8(s1) << 8) | (xf_clip8(s2) << 16);
+      hrow[(r0 - ra + rr) * n + ox] = clip8(s0) | (clip8(s1) << 8) | (clip8(s2) << 16);
     }
     __syncthreads();
   }
@@ -1416,7 +1412,7 @@ __global__ __launch_bounds__(XF_NT) void jpeg_transform_kernel(const uint8_t* __
     const int yy = i / n, x = i - yy * n, y = y0 + yy;
     const int bv = sbv[yy], yb = bv & 0xFFFF, ys = bv >> 16;
     const int32_t* k = skv + yy * xk.ksv;
-    int sc[3] = {1 << (XF_PREC - 1), 1 << (XF_PREC - 1), 1 << (XF_PREC - 1)};
+    int sc[3] = {1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1)};
     for (int j = 0; j < ys; ++j) {
       const uint32_t v = hrow[(yb + j) * n + x];
       const int w = k[j];
@@ -1426,76 +1422,251 @@ __global__ __launch_bounds__(XF_NT) void jpeg_transform_kernel(const uint8_t* __
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float v = ((float)xf_clip8(sc[c]) / 255.0f - xk.mean[c]) / xk.sd[c];
-      const int64_t o = (((int64_t)f * 3 + c) * n + y) * (int64_t)n + x;
-      if (OUT_BF16) ((uint16_t*)out)[o] = f2bf(v);
-      else ((float*)out)[o] = v;
+      const float v = to_tensor_normalize(clip8(sc[c]), xk.mean, xk.sd, c);
+      store_out<OUT_BF16>(out, (((int64_t)f * 3 + c) * n + y) * (int64_t)n + x, v);
     }
   }
 }
 
-}  // namespace
-
-// Workspace of the chunked entropy decode (after the coefficients and planes).
-struct JpWs {
-  size_t bytes;
-  size_t o_ustuff, o_cbase, o_ubase, o_ulen, o_cframe, o_cnt, o_coff, o_mk, o_x[2], o_nb[2], o_dc[2], o_ch[2],
-      o_bfirst, o_pred, o_fch, o_sso, o_sse, o_vf, o_cpx, o_cpn, o_cpd, o_tn, o_td;
-  int64_t nmax;
+// ---- host: geometry, workspace, the decode's stages ------------------------
+// Everything that follows from geom[JG_SLOTS] (internal.hpp JpegGeomSlot) and the frame count,
+// derived in one place for jpeg_decode and jpeg_workspace_bytes: the caller allocates what the one
+// returns and the other checks `ws_bytes < need` against it, so the two must agree byte for byte.
+struct JpegLayout {
+  int W, H;
+  JpegGeom g;
+  JpegPlanes pl;
+  JpegMcu mc;            // block walk of one MCU (component order, then rows, then columns within the component)
+  int cmode, cdw, cdh;   // chroma layout relative to luma (components 1, 2 share it): chroma_at's mode, size
+  int64_t plane_bytes;   // of one frame's component planes (= pl.plane_frame_bytes)
+  size_t coef_bytes;     // int16 coefficients of all frames
+  size_t base_bytes;     // coefficients + planes, rounded to 256: the chunk buffers start here
 };
 
-static JpWs jp_layout(int nframes, int64_t data_bytes) {
-  JpWs w{};
-  size_t off = 0;
-  auto carve = [&](size_t n) { const size_t o = off; off += (n + 255) & ~(size_t)255; return o; };
-  const int64_t B = nframes;
-  w.nmax = data_bytes / JP_CHUNK + B + 1;   // >= sum over frames of max(1, ceil(raw bytes / JP_CHUNK))
-  w.o_ustuff = carve((size_t)data_bytes + 4 * (size_t)B + 64);
-  w.o_cbase = carve((size_t)(B + 1) * 8);
-  w.o_ubase = carve((size_t)B * 8);
-  w.o_ulen = carve((size_t)B * 4);
-  w.o_cframe = carve((size_t)w.nmax * 4);
-  w.o_cnt = carve((size_t)w.nmax * 4);
-  w.o_coff = carve((size_t)w.nmax * 4);
-  w.o_mk = carve((size_t)w.nmax);
-  for (int i = 0; i < 2; ++i) {
-    w.o_x[i] = carve((size_t)w.nmax * 8);
-    w.o_nb[i] = carve((size_t)w.nmax * 4);
-    w.o_dc[i] = carve((size_t)w.nmax * 12);
-    w.o_ch[i] = carve((size_t)w.nmax);
+JpegLayout jpeg_layout(const int32_t* geom, int nframes) {
+  JpegLayout L{};
+  JpegGeom& g = L.g;
+  JpegPlanes& pl = L.pl;
+  const int W = L.W = geom[JG_W], H = L.H = geom[JG_H];
+  g.ncomp = geom[JG_NCOMP];
+  g.ri = geom[JG_RI];
+  g.nseg = geom[JG_NSEG];
+  // (mi_jpeg_workspace_bytes comes here with an unchecked geometry: sizes only, inside the arrays)
+  const int nc = std::min(std::max(g.ncomp, 0), 3);
+  // single-component scan: MCU = one block over ceil(W/8) x ceil(H/8), whatever its sampling factors
+  int hmax = 1, vmax = 1;
+  for (int c = 0; c < nc; ++c) {
+    g.hs[c] = g.ncomp == 3 ? geom[JG_HS + 2 * c] : 1;
+    g.vs[c] = g.ncomp == 3 ? geom[JG_VS + 2 * c] : 1;
+    hmax = std::max(hmax, g.hs[c]);
+    vmax = std::max(vmax, g.vs[c]);
   }
-  w.o_bfirst = carve((size_t)w.nmax * 8);
-  w.o_pred = carve((size_t)w.nmax * 12);
-  w.o_fch = carve((size_t)(JP_ROUNDS + 1) * B * 4);
-  w.o_sso = carve((size_t)B * 8);
-  w.o_sse = carve((size_t)B * 8);
-  w.o_vf = carve((size_t)B);
-  w.o_cpx = carve((size_t)w.nmax * JP_NCP * 8);
-  w.o_cpn = carve((size_t)w.nmax * JP_NCP * 4);
-  w.o_cpd = carve((size_t)w.nmax * JP_NCP * 12);
-  w.o_tn = carve((size_t)w.nmax * 4);
-  w.o_td = carve((size_t)w.nmax * 12);
+  g.mcux = (W + 8 * hmax - 1) / (8 * hmax);
+  g.mcuy = (H + 8 * vmax - 1) / (8 * vmax);
+  int64_t blocks = 0, bytes = 0;
+  for (int c = 0; c < nc; ++c) {
+    g.bw[c] = g.mcux * g.hs[c];
+    pl.bh[c] = g.mcuy * g.vs[c];
+    g.cbase[c] = (int)blocks;
+    blocks += (int64_t)g.bw[c] * pl.bh[c];
+    pl.pstride[c] = g.bw[c] * 8;
+    pl.pbase[c] = bytes;
+    bytes += (int64_t)pl.pstride[c] * pl.bh[c] * 8;
+    pl.qsel[c] = geom[JG_QSEL + c];
+    g.dcsel[c] = geom[JG_DCSEL + c];
+    g.acsel[c] = geom[JG_ACSEL + c];
+    for (int bv = 0; bv < g.vs[c]; ++bv)
+      for (int bh = 0; bh < g.hs[c] && L.mc.bpm < 16; ++bh) {
+        L.mc.comp[L.mc.bpm] = (int8_t)c;
+        L.mc.dh[L.mc.bpm] = (int8_t)bh;
+        L.mc.dv[L.mc.bpm] = (int8_t)bv;
+        ++L.mc.bpm;
+      }
+  }
+  g.blocks_per_frame = blocks;
+  pl.plane_frame_bytes = L.plane_bytes = bytes;
+  L.cdw = W;
+  L.cdh = H;
+  if (g.ncomp == 3 && g.hs[1] > 0 && g.vs[1] > 0) {
+    const int hr = hmax / g.hs[1], vr = vmax / g.vs[1];
+    L.cmode = (hr == 1 && vr == 1) ? 0 : (hr == 2 && vr == 1) ? 1 : 2;
+    L.cdw = (W * g.hs[1] + hmax - 1) / hmax;   // libjpeg downsampled_width
+    L.cdh = (H * g.vs[1] + vmax - 1) / vmax;
+  }
+  L.coef_bytes = (size_t)nframes * blocks * 64 * sizeof(int16_t);
+  L.base_bytes = (L.coef_bytes + (size_t)nframes * bytes + 255) & ~(size_t)255;
+  return L;
+}
+
+// The decode's workspace, listed once: coefficients and component planes, then (chunked decode
+// only) the chunk buffers, each on a 256-byte boundary.  The listing gives the total for
+// jpeg_workspace_bytes and the typed pointers for jpeg_decode; offsets are integers, and pointers
+// are formed only when there is a base (sizing runs with none).
+struct JpegWs {
+  size_t bytes;
+  int16_t* coef;
+  uint8_t* planes;
+  int64_t nmax;          // chunk slots: >= sum over frames of max(1, ceil(raw bytes / JP_CHUNK))
+  uint8_t* ustuff;       // the frames' unstuffed streams
+  int64_t *cbase, *ubase;
+  uint32_t* ulen;
+  int32_t *cframe, *cnt;
+  uint32_t* coff;
+  uint8_t* mk;
+  JpState st[2];         // the sync rounds' double buffer
+  int64_t* bfirst;
+  int32_t *pred, *fch;   // fch: [JP_ROUNDS + 1][B] a frame's chunks changed in round r
+  int64_t *sso, *sse;    // sanitised segments (jp_layout_kernel)
+  uint8_t* vf;
+  JpCps cps;
+};
+
+JpegWs jpeg_workspace(const JpegLayout& L, int nframes, int64_t data_bytes, bool chunked, void* base) {
+  JpegWs w{};
+  size_t off = 0;
+  auto take = [&](auto*& p, size_t n) {
+    if (base) p = (std::remove_reference_t<decltype(p)>)((char*)base + off);
+    off += n;
+  };
+  auto carve = [&](auto*& p, size_t n) { take(p, (n + 255) & ~(size_t)255); };
+  take(w.coef, L.coef_bytes);
+  take(w.planes, L.base_bytes - L.coef_bytes);
+  if (chunked) {
+    const size_t B = (size_t)nframes, nmax = (size_t)(w.nmax = data_bytes / JP_CHUNK + nframes + 1);
+    carve(w.ustuff, (size_t)data_bytes + 4 * B + 64);
+    carve(w.cbase, (B + 1) * 8);
+    carve(w.ubase, B * 8);
+    carve(w.ulen, B * 4);
+    carve(w.cframe, nmax * 4);
+    carve(w.cnt, nmax * 4);
+    carve(w.coff, nmax * 4);
+    carve(w.mk, nmax);
+    for (JpState& st : w.st) {
+      carve(st.x, nmax * 8);
+      carve(st.nb, nmax * 4);
+      carve(st.dc, nmax * 12);
+      carve(st.changed, nmax);
+    }
+    carve(w.bfirst, nmax * 8);
+    carve(w.pred, nmax * 12);
+    carve(w.fch, (size_t)(JP_ROUNDS + 1) * B * 4);
+    carve(w.sso, B * 8);
+    carve(w.sse, B * 8);
+    carve(w.vf, B);
+    carve(w.cps.x, nmax * JP_NCP * 8);
+    carve(w.cps.nb, nmax * JP_NCP * 4);
+    carve(w.cps.dc, nmax * JP_NCP * 12);
+    carve(w.cps.tn, nmax * 4);
+    carve(w.cps.td, nmax * 12);
+  }
   w.bytes = off;
   return w;
 }
 
-// A/B timing probes (MICLIP_JPEG_ABL): bit 0 = the final pass decodes without storing coefficients
-static int jp_abl() {
-#if MICLIP_AB
-  const char* e = getenv("MICLIP_JPEG_ABL");
-  return e ? atoi(e) : 0;
-#else
-  return 0;
-#endif
+// mi_jpeg_decode's inputs, as every stage takes them
+struct JpegIn {
+  const uint8_t* data;
+  int64_t data_bytes;
+  const int64_t *seg_off, *seg_end;
+  const JpegHuff* huff;
+  const int32_t* huff_idx;
+  int nsets;
+  const uint16_t* qtab;
+  int nframes;
+  hipStream_t s;
+  // dynamic LDS of the entropy kernels' <LDS_T = true> instantiations: the table sets (0: the sets
+  // do not fit, or there is no set index -- tables from global memory, <false>)
+  size_t table_lds() const {
+    return huff_idx && nsets >= 1 && nsets <= JPEG_LDS_SETS ? nsets * 4 * sizeof(JpegHuff) : 0;
+  }
+};
+
+// Serial entropy stage: the lane-per-(frame, segment) kernel.  With `skip` it is the chunked
+// stage's fix-up pass over the frames outside the chunk layout, tables from global memory.
+hipError_t entropy_serial(const JpegIn& in, const JpegLayout& L, const JpegWs& w, const uint8_t* skip) {
+  const int64_t lanes = (int64_t)in.nframes * L.g.nseg;
+  const int eg = (int)((lanes + 63) / 64);
+  const size_t tl = skip ? 0 : in.table_lds();
+  return with_value<0, 1>(tl != 0, [&](auto lt) {
+    return launch_kernel<jpeg_entropy_kernel<decltype(lt)::value != 0>>(eg, 64, tl, in.s, in.data, in.seg_off, in.seg_end,
+                                                                       in.huff, in.huff_idx, in.nsets, L.g, in.nframes,
+                                                                       w.coef, in.data_bytes, skip);
+  });
 }
 
-static bool jp_serial_forced() {
-#if MICLIP_AB
-  const char* e = getenv("MICLIP_JPEG_SERIAL");   // A/B: the lane-per-frame entropy kernel for every scan
-  return e && e[0] == '1';
-#else
-  return false;
-#endif
+// Chunked entropy stage (scans without restart markers): layout, unstuff, phase 1 + JP_ROUNDS
+// consistency rounds, prefix sums, the final pass, then the fix-up of the out-of-layout frames
+hipError_t entropy_chunked(const JpegIn& in, const JpegLayout& L, const JpegWs& w) {
+  const int nframes = in.nframes;
+  const hipStream_t s = in.s;
+  hipError_t e;
+  if ((e = hipMemsetAsync(w.cframe, 0xFF, (size_t)w.nmax * 4, s)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(w.fch, 0, (size_t)(JP_ROUNDS + 1) * nframes * 4, s)) != hipSuccess) return e;
+  const dim3 fg((unsigned)((nframes + 255) / 256)), ug((unsigned)w.nmax);
+  const int cg = (int)((w.nmax + 255) / 256);
+  const JpChunks ch{w.cbase, w.cframe, w.ubase, w.ulen};
+  if ((e = launch_kernel(jp_layout_kernel, dim3(1), 1024, s, in.seg_off, in.seg_end, nframes, in.data_bytes, w.cbase,
+                         w.ubase, w.sso, w.sse, w.vf)) != hipSuccess)
+    return e;
+  if ((e = launch_kernel(jp_chunk_frame_kernel, fg, 256, s, w.cbase, nframes, w.cframe)) != hipSuccess) return e;
+  if ((e = launch_kernel(jp_unstuff_count_kernel, ug, 256, s, in.data, w.sso, w.sse, ch, w.cnt, w.mk)) != hipSuccess)
+    return e;
+  if ((e = launch_kernel(jp_unstuff_scan_kernel, fg, 256, s, ch, nframes, w.cnt, w.mk, w.coff, w.ulen)) != hipSuccess)
+    return e;
+  if ((e = launch_kernel(jp_unstuff_scatter_kernel, ug, 256, s, in.data, w.sso, w.sse, ch, w.cnt, w.coff, w.ustuff)) !=
+      hipSuccess)
+    return e;
+  const size_t tl = in.table_lds();
+  const JpState& fin = w.st[JP_ROUNDS & 1];
+  const int32_t* last_changed = w.fch + (int64_t)JP_ROUNDS * nframes;
+  // A/B timing probes (MICLIP_JPEG_ABL): bit 0 = the final pass decodes without storing coefficients
+  const int abl = ab_env_int("MICLIP_JPEG_ABL", 0);
+  e = with_value<0, 1>(tl != 0, [&](auto lt) {
+    constexpr bool LDS_T = decltype(lt)::value != 0;
+    for (int r = 0; r <= JP_ROUNDS; ++r) {
+      const JpState& src = w.st[(r + 1) & 1];   // round r reads round r - 1's buffer
+      const JpState& dst = w.st[r & 1];
+      const hipError_t er =
+          launch_kernel<jp_sync_kernel<LDS_T>>(cg, 256, tl, s, w.ustuff, ch, w.nmax, in.huff, in.huff_idx, in.nsets, L.g,
+                                               L.mc, r, src, dst, w.fch + (int64_t)r * nframes, w.cps);
+      if (er != hipSuccess) return er;
+    }
+    const hipError_t ep = launch_kernel(jp_prefix_kernel, fg, 256, s, ch, nframes, fin, w.bfirst, w.pred);
+    if (ep != hipSuccess) return ep;
+    return launch_kernel<jp_final_kernel<LDS_T>>(cg, 256, tl, s, w.ustuff, ch, w.nmax, in.huff, in.huff_idx, in.nsets, L.g,
+                                                 L.mc, fin, w.bfirst, w.pred, last_changed, w.coef, abl);
+  });
+  if (e != hipSuccess) return e;
+  // frames outside the chunk layout (repeated / out-of-order segments): the serial decode
+  return entropy_serial(in, L, w, w.vf);
+}
+
+// IDCT stage: coefficients -> component planes, a thread per block
+hipError_t idct_stage(const JpegIn& in, const JpegLayout& L, const JpegWs& w) {
+  const int64_t blocks = L.g.blocks_per_frame, fc = frames_per_launch(blocks, in.nframes);
+  for (int64_t f0 = 0; f0 < in.nframes; f0 += fc) {
+    const int nfc = (int)std::min<int64_t>(fc, in.nframes - f0);
+    const int64_t nb = (int64_t)nfc * blocks;
+    const hipError_t e = launch_kernel(jpeg_idct_kernel, dim3((unsigned)((nb + 255) / 256)), 256, in.s,
+                                       w.coef + f0 * blocks * 64, in.qtab + f0 * 4 * 64, L.g, L.pl, nfc,
+                                       w.planes + f0 * L.plane_bytes);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// RGB output stage: upsampling + colour conversion, a thread per 4 pixels
+hipError_t rgb_stage(const JpegIn& in, const JpegLayout& L, const JpegWs& w, uint8_t* out_rgb) {
+  const int64_t px = (int64_t)L.W * L.H, fc = frames_per_launch(px, in.nframes);
+  for (int64_t f0 = 0; f0 < in.nframes; f0 += fc) {
+    const int nfc = (int)std::min<int64_t>(fc, in.nframes - f0);
+    const int64_t np = (int64_t)nfc * px;
+    const hipError_t e = launch_kernel(jpeg_color_kernel, dim3((unsigned)((np / 4 + 256) / 256)), 256, in.s,
+                                       w.planes + f0 * L.plane_bytes, L.pl, L.W, L.H, L.g.ncomp, L.cmode, L.cdw, L.cdh,
+                                       nfc, out_rgb + f0 * px * 3);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 // The fused transform's launch shape: output rows per workgroup (band) and LDS bytes -- the
@@ -1517,13 +1688,7 @@ hipError_t jpeg_xform_plan(int H, int W, int n, int mode, XformK& xk, size_t& ld
   xk.W = W;
   xk.i24 = t.wmax < (1 << 23);
   if (xk.xw / 4 > XF_NT * XF_IPT) return hipErrorInvalidValue;   // wider than one step's row: decode + preprocess
-  // torchvision's Normalize constants: Python floats -> float32 (preprocess.hip)
-  const float mean[3] = {(float)0.48145466, (float)0.4578275, (float)0.40821073};
-  const float sd[3] = {(float)0.26862954, (float)0.26130258, (float)0.27577711};
-  for (int c = 0; c < 3; ++c) {
-    xk.mean[c] = mean[c];
-    xk.sd[c] = sd[c];
-  }
+  clip_norm(xk.mean, xk.sd);
   // the widest band that leaves two workgroups per CU (<= XF_LDS2), else one (<= 150 KB)
   for (const size_t cap : {XF_LDS2, (size_t)150 * 1024}) {
     for (int band = 16; band >= 1; band /= 2) {
@@ -1546,6 +1711,31 @@ hipError_t jpeg_xform_plan(int H, int W, int n, int mode, XformK& xk, size_t& ld
   return hipErrorInvalidValue;   // a source too wide / tall for one band in LDS: decode + preprocess instead
 }
 
+// Fused output stage: colour + resample + crop + normalise (jpeg_transform_kernel), a workgroup
+// per (frame, band); its 78 to 150 KB of dynamic LDS need the raised limit of launch_kernel<KERNEL>
+hipError_t transform_stage(const JpegIn& in, const JpegLayout& L, const JpegWs& w, const JpegXform& xf) {
+  XformK xk{};
+  size_t lds = 0;
+  hipError_t e = jpeg_xform_plan(L.H, L.W, xf.n, xf.mode, xk, lds);
+  if (e != hipSuccess) return e;
+  const int64_t fc = frames_per_launch((int64_t)xk.nbands * XF_NT, in.nframes, 0x7fffffff);
+  for (int64_t f0 = 0; f0 < in.nframes; f0 += fc) {
+    const int nfc = (int)std::min<int64_t>(fc, in.nframes - f0);
+    void* o = (char*)xf.out + f0 * 3 * (int64_t)xf.n * xf.n * (xf.out_bf16 ? 2 : 4);
+    const int grid = (int)((int64_t)nfc * xk.nbands);
+    e = with_value<0, 1>(xf.out_bf16 != 0, [&](auto bf) {
+      return with_value<0, 1>(xk.i24 != 0, [&](auto i24) {
+        return launch_kernel<jpeg_transform_kernel<decltype(bf)::value != 0, decltype(i24)::value != 0>>(
+            grid, XF_NT, lds, in.s, w.planes + f0 * L.plane_bytes, L.pl, L.g.ncomp, L.cmode, L.cdw, L.cdh, xk, o);
+      });
+    });
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace
+
 // Whether the fused transform has a launch plan for H x W -> n (mi_jpeg_decode_transform checks
 // this before any decode work is queued)
 bool jpeg_xform_fits(int H, int W, int n, int mode) {
@@ -1558,206 +1748,24 @@ bool jpeg_xform_fits(int H, int W, int n, int mode) {
 hipError_t jpeg_decode(const uint8_t* data, int64_t data_bytes, const int64_t* seg_off, const int64_t* seg_end,
                        const void* huff, const int32_t* huff_idx, int nsets, const uint16_t* qtab, const int32_t* geom,
                        int nframes, uint8_t* out_rgb, void* ws, size_t ws_bytes, hipStream_t s, const JpegXform* xf) {
-  // geom: [W, H, ncomp, ri, nseg, hs0, vs0, hs1, vs1, hs2, vs2, q0, q1, q2, dc0, dc1, dc2, ac0, ac1, ac2]
-  const int W = geom[0], H = geom[1], ncomp = geom[2];
-  JpegGeom g{};
-  g.ncomp = ncomp;
-  g.ri = geom[3];
-  g.nseg = geom[4];
-  int hmax = 1, vmax = 1;
-  for (int c = 0; c < ncomp; ++c) {
-    g.hs[c] = geom[5 + 2 * c];
-    g.vs[c] = geom[6 + 2 * c];
-    hmax = g.hs[c] > hmax ? g.hs[c] : hmax;
-    vmax = g.vs[c] > vmax ? g.vs[c] : vmax;
-  }
-  if (ncomp == 1) {   // single-component scan: MCU = one block over ceil(W/8) x ceil(H/8)
-    g.hs[0] = g.vs[0] = 1;
-    hmax = vmax = 1;
-  }
-  g.mcux = (W + 8 * hmax - 1) / (8 * hmax);
-  g.mcuy = (H + 8 * vmax - 1) / (8 * vmax);
-  JpegPlanes pl{};
-  int64_t blocks = 0, bytes = 0;
-  for (int c = 0; c < ncomp; ++c) {
-    g.bw[c] = g.mcux * g.hs[c];
-    pl.bh[c] = g.mcuy * g.vs[c];
-    g.cbase[c] = (int)blocks;
-    blocks += (int64_t)g.bw[c] * pl.bh[c];
-    pl.pstride[c] = g.bw[c] * 8;
-    pl.pbase[c] = bytes;
-    bytes += (int64_t)pl.pstride[c] * pl.bh[c] * 8;
-    pl.qsel[c] = geom[11 + c];
-    g.dcsel[c] = geom[14 + c];
-    g.acsel[c] = geom[17 + c];
-  }
-  g.blocks_per_frame = blocks;
-  pl.plane_frame_bytes = bytes;
-  const size_t coef_bytes = (size_t)nframes * blocks * 64 * sizeof(int16_t);
-  const size_t base_bytes = (coef_bytes + (size_t)nframes * bytes + 255) & ~(size_t)255;
-  const bool chunked = g.nseg == 1 && !jp_serial_forced();
-  const JpWs jw = jp_layout(nframes, data_bytes);
-  if (ws_bytes < base_bytes + (chunked ? jw.bytes : 0)) return hipErrorInvalidValue;
-  int16_t* coef = (int16_t*)ws;
-  uint8_t* planes = (uint8_t*)ws + coef_bytes;
-  hipError_t e = hipMemsetAsync(coef, 0, coef_bytes, s);
+  const JpegIn in{data, data_bytes, seg_off, seg_end, (const JpegHuff*)huff, huff_idx, nsets, qtab, nframes, s};
+  const JpegLayout L = jpeg_layout(geom, nframes);
+  // scans without restart markers take the chunked decode (A/B: MICLIP_JPEG_SERIAL != 0 forces the
+  // lane-per-frame entropy kernel for every scan)
+  const bool chunked = L.g.nseg == 1 && ab_env_int("MICLIP_JPEG_SERIAL", 0) == 0;
+  const JpegWs w = jpeg_workspace(L, nframes, data_bytes, chunked, ws);
+  if (ws_bytes < w.bytes) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(w.coef, 0, L.coef_bytes, s);   // the entropy stages write nonzero coefficients only
   if (e != hipSuccess) return e;
-  const bool lds_t = huff_idx && nsets >= 1 && nsets <= JPEG_LDS_SETS;
-  if (chunked) {
-    char* w = (char*)ws + base_bytes;
-    uint8_t* ustuff = (uint8_t*)(w + jw.o_ustuff);
-    int64_t* cbase = (int64_t*)(w + jw.o_cbase);
-    int64_t* ubase = (int64_t*)(w + jw.o_ubase);
-    uint32_t* ulen = (uint32_t*)(w + jw.o_ulen);
-    int32_t* cframe = (int32_t*)(w + jw.o_cframe);
-    int32_t* cnt = (int32_t*)(w + jw.o_cnt);
-    uint32_t* coff = (uint32_t*)(w + jw.o_coff);
-    uint8_t* mk = (uint8_t*)(w + jw.o_mk);
-    JpState st[2];
-    for (int i = 0; i < 2; ++i)
-      st[i] = JpState{(uint64_t*)(w + jw.o_x[i]), (int32_t*)(w + jw.o_nb[i]), (int32_t*)(w + jw.o_dc[i]),
-                      (uint8_t*)(w + jw.o_ch[i])};
-    int64_t* bfirst = (int64_t*)(w + jw.o_bfirst);
-    int32_t* pred = (int32_t*)(w + jw.o_pred);
-    int32_t* fch = (int32_t*)(w + jw.o_fch);
-    int64_t* sso = (int64_t*)(w + jw.o_sso);
-    int64_t* sse = (int64_t*)(w + jw.o_sse);
-    uint8_t* vf = (uint8_t*)(w + jw.o_vf);
-    const JpCps cps{(uint64_t*)(w + jw.o_cpx), (int32_t*)(w + jw.o_cpn), (int32_t*)(w + jw.o_cpd),
-                    (int32_t*)(w + jw.o_tn), (int32_t*)(w + jw.o_td)};
-    const int64_t nmax = jw.nmax;
-    if ((e = hipMemsetAsync(cframe, 0xFF, (size_t)nmax * 4, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(fch, 0, (size_t)(JP_ROUNDS + 1) * nframes * 4, s)) != hipSuccess) return e;
-    // block walk of one MCU (component order, then rows, then columns within the component)
-    JpegMcu mc{};
-    for (int c = 0; c < ncomp; ++c)
-      for (int bv = 0; bv < g.vs[c]; ++bv)
-        for (int bh = 0; bh < g.hs[c]; ++bh) {
-          mc.comp[mc.bpm] = (int8_t)c;
-          mc.dh[mc.bpm] = (int8_t)bh;
-          mc.dv[mc.bpm] = (int8_t)bv;
-          ++mc.bpm;
-        }
-    const dim3 fg((unsigned)((nframes + 255) / 256)), cg((unsigned)((nmax + 255) / 256)),
-        fg4((unsigned)((nframes + 63) / 64));
-    hipLaunchKernelGGL(jp_layout_kernel, dim3(1), dim3(1024), 0, s, seg_off, seg_end, nframes, data_bytes, cbase, ubase,
-                       sso, sse, vf);
-    hipLaunchKernelGGL(jp_chunk_frame_kernel, fg, dim3(256), 0, s, cbase, nframes, cframe);
-    const JpChunks ch{cbase, cframe, ubase, ulen};
-    hipLaunchKernelGGL(jp_unstuff_count_kernel, dim3((unsigned)nmax), dim3(256), 0, s, data, sso, sse, ch, cnt, mk);
-    hipLaunchKernelGGL(jp_unstuff_scan_kernel, fg, dim3(256), 0, s, ch, nframes, cnt, mk, coff, ulen);
-    hipLaunchKernelGGL(jp_unstuff_scatter_kernel, dim3((unsigned)nmax), dim3(256), 0, s, data, sso, sse, ch, cnt, coff,
-                       ustuff);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const size_t tl = lds_t ? nsets * 4 * sizeof(JpegHuff) : 0;
-    for (int r = 0; r <= JP_ROUNDS; ++r) {
-      const JpState& src = st[(r + 1) & 1];   // round r reads round r - 1's buffer
-      const JpState& dst = st[r & 1];
-      if (lds_t)
-        hipLaunchKernelGGL(jp_sync_kernel<true>, cg, dim3(256), tl, s, ustuff, ch, nmax, (const JpegHuff*)huff,
-                           huff_idx, nsets, g, mc, r, src, dst, fch + (int64_t)r * nframes, cps);
-      else
-        hipLaunchKernelGGL(jp_sync_kernel<false>, cg, dim3(256), 0, s, ustuff, ch, nmax, (const JpegHuff*)huff,
-                           huff_idx, nsets, g, mc, r, src, dst, fch + (int64_t)r * nframes, cps);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    const JpState& fin = st[JP_ROUNDS & 1];
-    hipLaunchKernelGGL(jp_prefix_kernel, fg, dim3(256), 0, s, ch, nframes, fin, bfirst, pred);
-    const int32_t* last_changed = fch + (int64_t)JP_ROUNDS * nframes;
-    if (lds_t)
-      hipLaunchKernelGGL(jp_final_kernel<true>, cg, dim3(256), tl, s, ustuff, ch, nmax, (const JpegHuff*)huff,
-                         huff_idx, nsets, g, mc, fin, bfirst, pred, last_changed, coef, jp_abl());
-    else
-      hipLaunchKernelGGL(jp_final_kernel<false>, cg, dim3(256), 0, s, ustuff, ch, nmax, (const JpegHuff*)huff,
-                         huff_idx, nsets, g, mc, fin, bfirst, pred, last_changed, coef, jp_abl());
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    // frames outside the chunk layout (repeated / out-of-order segments): the serial decode
-    hipLaunchKernelGGL(jpeg_entropy_kernel<false>, fg4, dim3(64), 0, s, data, seg_off, seg_end, (const JpegHuff*)huff,
-                       huff_idx, nsets, g, nframes, coef, data_bytes, (const uint8_t*)vf);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  } else {
-    const int64_t lanes = (int64_t)nframes * g.nseg;
-    const dim3 eg((unsigned)((lanes + 63) / 64));
-    if (lds_t)
-      hipLaunchKernelGGL(jpeg_entropy_kernel<true>, eg, dim3(64), nsets * 4 * sizeof(JpegHuff), s, data, seg_off,
-                         seg_end, (const JpegHuff*)huff, huff_idx, nsets, g, nframes, coef, data_bytes,
-                         (const uint8_t*)nullptr);
-    else
-      hipLaunchKernelGGL(jpeg_entropy_kernel<false>, eg, dim3(64), 0, s, data, seg_off, seg_end,
-                         (const JpegHuff*)huff, huff_idx, nsets, g, nframes, coef, data_bytes, (const uint8_t*)nullptr);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  // A dispatch counts its work-items in 32 bits (grid x block < 2^32): the
-  // per-block and per-pixel kernels run over frame chunks of < 2^31 items.
-  const int64_t fc_idct = blocks > 0 ? std::max<int64_t>(1, ((int64_t)1 << 31) / blocks) : nframes;
-  for (int64_t f0 = 0; f0 < nframes; f0 += fc_idct) {
-    const int nfc = (int)std::min<int64_t>(fc_idct, nframes - f0);
-    const int64_t nb = (int64_t)nfc * blocks;
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s,
-                       coef + f0 * blocks * 64, qtab + f0 * 4 * 64, g, pl, nfc, planes + f0 * bytes);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  // chroma layout relative to luma (components 1, 2 share it)
-  int cmode = 0, cdw = W, cdh = H;
-  if (ncomp == 3) {
-    const int hr = hmax / g.hs[1], vr = vmax / g.vs[1];
-    cmode = (hr == 1 && vr == 1) ? 0 : (hr == 2 && vr == 1) ? 1 : 2;
-    cdw = (W * g.hs[1] + hmax - 1) / hmax;   // libjpeg downsampled_width
-    cdh = (H * g.vs[1] + vmax - 1) / vmax;
-  }
-  if (xf) {   // fused colour + resample + crop + normalise (jpeg_transform_kernel)
-    XformK xk{};
-    size_t lds = 0;
-    if ((e = jpeg_xform_plan(H, W, xf->n, xf->mode, xk, lds)) != hipSuccess) return e;
-    const int64_t per_launch = std::max<int64_t>(1, (int64_t)0x7fffffff / ((int64_t)xk.nbands * XF_NT));
-    for (int64_t f0 = 0; f0 < nframes; f0 += per_launch) {
-      const int nfc = (int)std::min<int64_t>(per_launch, nframes - f0);
-      char* o = (char*)xf->out + f0 * 3 * (int64_t)xf->n * xf->n * (xf->out_bf16 ? 2 : 4);
-      const dim3 grid((unsigned)((int64_t)nfc * xk.nbands));
-#define XF_LAUNCH(BF, I24_)                                                                                      \
-  hipLaunchKernelGGL((jpeg_transform_kernel<BF, I24_>), grid, dim3(XF_NT), lds, s, planes + f0 * bytes, pl, ncomp, \
-                     cmode, cdw, cdh, xk, (void*)o)
-      if (xf->out_bf16) {
-        if (xk.i24) XF_LAUNCH(true, true);
-        else XF_LAUNCH(true, false);
-      } else {
-        if (xk.i24) XF_LAUNCH(false, true);
-        else XF_LAUNCH(false, false);
-      }
-#undef XF_LAUNCH
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
-  const int64_t px = (int64_t)W * H;
-  const int64_t fc_px = std::max<int64_t>(1, ((int64_t)1 << 31) / px);
-  for (int64_t f0 = 0; f0 < nframes; f0 += fc_px) {
-    const int nfc = (int)std::min<int64_t>(fc_px, nframes - f0);
-    const int64_t np = (int64_t)nfc * px;
-    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((np / 4 + 256) / 256)), dim3(256), 0, s, planes + f0 * bytes, pl,
-                       W, H, ncomp, cmode, cdw, cdh, nfc, out_rgb + f0 * px * 3);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  if ((e = chunked ? entropy_chunked(in, L, w) : entropy_serial(in, L, w, nullptr)) != hipSuccess) return e;
+  if ((e = idct_stage(in, L, w)) != hipSuccess) return e;
+  return xf ? transform_stage(in, L, w, *xf) : rgb_stage(in, L, w, out_rgb);
 }
 
+// (sized for the chunked decode whenever the scan has no restart markers, forced serial or not)
 size_t jpeg_workspace_bytes(const int32_t* geom, int nframes, int64_t data_bytes) {
-  const int W = geom[0], H = geom[1], ncomp = geom[2];
-  int hmax = 1, vmax = 1, hs[3] = {1, 1, 1}, vs[3] = {1, 1, 1};
-  for (int c = 0; c < ncomp && ncomp == 3; ++c) {
-    hs[c] = geom[5 + 2 * c];
-    vs[c] = geom[6 + 2 * c];
-    hmax = hs[c] > hmax ? hs[c] : hmax;
-    vmax = vs[c] > vmax ? vs[c] : vmax;
-  }
-  const int64_t mcux = (W + 8 * hmax - 1) / (8 * hmax), mcuy = (H + 8 * vmax - 1) / (8 * vmax);
-  int64_t blocks = 0;
-  for (int c = 0; c < ncomp; ++c) blocks += mcux * hs[c] * mcuy * vs[c];
-  const size_t base = ((size_t)nframes * blocks * 64 * (sizeof(int16_t) + 1) + 255) & ~(size_t)255;
-  return base + (geom[4] == 1 ? jp_layout(nframes, data_bytes < 0 ? 0 : data_bytes).bytes : 0);
+  const JpegLayout L = jpeg_layout(geom, nframes);
+  return jpeg_workspace(L, nframes, data_bytes < 0 ? 0 : data_bytes, L.g.nseg == 1, nullptr).bytes;
 }
 
 }  // namespace miclip

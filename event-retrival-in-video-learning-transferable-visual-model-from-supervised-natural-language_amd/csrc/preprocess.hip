@@ -36,13 +36,8 @@ namespace miclip {
 
 namespace {
 
-constexpr int PREC = 22;  // Pillow PRECISION_BITS = 32 - 8 - 2
-
-__device__ __forceinline__ uint32_t clip8(int acc) {
-  acc >>= PREC;
-  return acc < 0 ? 0u : (acc > 255 ? 255u : (uint32_t)acc);
-}
-
+// (PRECISION_BITS, clip8, the Normalize constants and the ToTensor / Normalize expression: common.hpp,
+// shared with jpeg.hip's fused transform)
 // one thread per (frame, tmp row, crop column), 3 channels
 __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ tmp,
                                                          const int32_t* __restrict__ kh,
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restri
   const int xb = bh[2 * x], xs = bh[2 * x + 1];
   const int32_t* k = kh + (int64_t)x * ksize;
   const uint8_t* p = src + ((b * H + r0 + r) * (int64_t)W + xb) * 3;
-  int s0 = 1 << (PREC - 1), s1 = s0, s2 = s0;
+  int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
   for (int j = 0; j < xs; ++j) {
     const int w = k[j];
     s0 += (int)p[3 * j] * w;
@@ -80,7 +75,6 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restri
                                                          const int32_t* __restrict__ kv,
                                                          const int32_t* __restrict__ bv, int ksize, int rows,
                                                          int n, int r0, Norm nm, int64_t total) {
-#pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int x = (int)(i % n);
@@ -89,7 +83,7 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restri
   const int yb = bv[2 * y] - r0, ys = bv[2 * y + 1];
   const int32_t* k = kv + (int64_t)y * ksize;
   const uint8_t* p = tmp + ((b * rows + yb) * (int64_t)n + x) * 3;
-  int s[3] = {1 << (PREC - 1), 1 << (PREC - 1), 1 << (PREC - 1)};
+  int s[3] = {1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1)};
   for (int j = 0; j < ys; ++j) {
     const int w = k[j];
     const uint8_t* q = p + (int64_t)j * n * 3;
@@ -99,11 +93,8 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restri
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    // torchvision ToTensor (x / 255) then Normalize ((x - mean) / std), f32, no contraction
-    const float v = ((float)clip8(s[c]) / 255.0f - nm.mean[c]) / nm.std[c];
-    const int64_t o = ((b * 3 + c) * n + y) * (int64_t)n + x;
-    if (OUT_BF16) ((uint16_t*)out)[o] = f2bf(v);
-    else ((float*)out)[o] = v;
+    const float v = to_tensor_normalize(clip8(s[c]), nm.mean, nm.std, c);
+    store_out<OUT_BF16>(out, ((b * 3 + c) * n + y) * (int64_t)n + x, v);
   }
 }
 
@@ -148,18 +139,10 @@ Geometry geometry(int H, int W, int n, int mode) {
   return g;
 }
 
-// Device copies of the coefficient tables per (device, H, W, n, mode),
+// Device copies of the coefficient tables (ResampleTables, internal.hpp) per (device, H, W, n, mode),
 // uploaded once (the only allocation of the preprocessing path).
-struct Tables {
-  int32_t *kh = nullptr, *bh = nullptr, *kv = nullptr, *bv = nullptr;
-  int ksh = 0, ksv = 0, r0 = 0, rows = 0;
-  int xlo = 0, xw = 0;            // source columns the crop's taps read: [xlo, xlo + xw)
-  std::vector<int32_t> hbv;       // host copy of bv (the fused JPEG transform sizes its row bands from it)
-  int32_t wmax = 0;               // largest |coefficient| of kh / kv (24-bit multiplies apply below 2^23)
-};
-
 std::mutex g_tab_mu;
-std::map<std::tuple<int, int, int, int, int>, Tables> g_tables;
+std::map<std::tuple<int, int, int, int, int>, ResampleTables> g_tables;
 
 // coefficients of the crop's outputs [off, off + n) of an in_size -> out_size resize
 int crop_coeffs(int in_size, int out_size, int off, int n, int filter, std::vector<int32_t>& kk,
@@ -168,7 +151,7 @@ int crop_coeffs(int in_size, int out_size, int off, int n, int filter, std::vect
   int ks;
   if (in_size == out_size) {  // the pass Pillow skips: identity rows
     ks = 1;
-    k_all.assign(out_size, 1 << PREC);
+    k_all.assign(out_size, 1 << PRECISION_BITS);
     b_all.resize(2 * out_size);
     for (int i = 0; i < out_size; ++i) {
       b_all[2 * i] = i;
@@ -183,7 +166,9 @@ int crop_coeffs(int in_size, int out_size, int off, int n, int filter, std::vect
   return ks;
 }
 
-hipError_t get_tables(int H, int W, int n, int mode, Tables& out) {
+}  // namespace
+
+hipError_t resample_tables(int H, int W, int n, int mode, ResampleTables& out) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
@@ -196,7 +181,7 @@ hipError_t get_tables(int H, int W, int n, int mode, Tables& out) {
   }
   const Geometry g = geometry(H, W, n, mode);
   std::vector<int32_t> kh, bh, kv, bv;
-  Tables t;
+  ResampleTables t;
   t.ksh = crop_coeffs(W, g.nw, g.left, n, g.filter, kh, bh);
   t.ksv = crop_coeffs(H, g.nh, g.top, n, g.filter, kv, bv);
   if (t.ksh < 0 || t.ksv < 0) return hipErrorInvalidValue;
@@ -234,8 +219,6 @@ hipError_t get_tables(int H, int W, int n, int mode, Tables& out) {
   out = t;
   return hipSuccess;
 }
-
-}  // namespace
 
 int resample_coeffs(int in_size, double in0, double in1, int out_size, int filter, std::vector<int32_t>& kk,
                     std::vector<int32_t>& bounds) {
@@ -277,25 +260,8 @@ int resample_coeffs(int in_size, double in0, double in1, int out_size, int filte
   // normalize_coeffs_8bpc: round half away from zero to 22 fractional bits
   kk.assign(pre.size(), 0);
   for (size_t i = 0; i < pre.size(); ++i)
-    kk[i] = pre[i] < 0 ? (int32_t)(-0.5 + pre[i] * (1 << PREC)) : (int32_t)(0.5 + pre[i] * (1 << PREC));
+    kk[i] = pre[i] < 0 ? (int32_t)(-0.5 + pre[i] * (1 << PRECISION_BITS)) : (int32_t)(0.5 + pre[i] * (1 << PRECISION_BITS));
   return ksize;
-}
-
-hipError_t resample_tables(int H, int W, int n, int mode, ResampleTables& r) {
-  Tables t;
-  const hipError_t e = get_tables(H, W, n, mode, t);
-  if (e != hipSuccess) return e;
-  r.kh = t.kh;
-  r.bh = t.bh;
-  r.kv = t.kv;
-  r.bv = t.bv;
-  r.ksh = t.ksh;
-  r.ksv = t.ksv;
-  r.xlo = t.xlo;
-  r.xw = t.xw;
-  r.hbv = t.hbv;
-  r.wmax = t.wmax;
-  return hipSuccess;
 }
 
 size_t preprocess_workspace_bytes(int64_t B, int H, int W, int n, int mode) {
@@ -307,33 +273,28 @@ size_t preprocess_workspace_bytes(int64_t B, int H, int W, int n, int mode) {
 hipError_t preprocess_frames(const uint8_t* frames, int64_t B, int H, int W, int n, int mode, void* out,
                              int out_bf16, void* ws, hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  Tables t;
-  hipError_t e = get_tables(H, W, n, mode, t);
+  ResampleTables t;
+  hipError_t e = resample_tables(H, W, n, mode, t);
   if (e != hipSuccess) return e;
-  // the constants as torchvision builds them: Python floats (double) -> float32
-  const Norm nm = {{(float)0.48145466, (float)0.4578275, (float)0.40821073},
-                   {(float)0.26862954, (float)0.26130258, (float)0.27577711}};
-  // A dispatch counts its work-items in 32 bits (grid x block < 2^32): big
-  // batches run as several launches of at most 2^31 work-items each.
-  const int64_t per = (int64_t)t.rows * n > (int64_t)n * n ? (int64_t)t.rows * n : (int64_t)n * n;
-  const int64_t bc = per > 0 ? (((int64_t)1 << 31) / per > 0 ? ((int64_t)1 << 31) / per : 1) : B;
+  Norm nm;
+  clip_norm(nm.mean, nm.std);
+  // big batches run as several launches (frames_per_launch: the larger pass's work-items per frame)
+  const int64_t bc = frames_per_launch(std::max((int64_t)t.rows * n, (int64_t)n * n), B);
   for (int64_t f0 = 0; f0 < B; f0 += bc) {
-    const int64_t nb = B - f0 < bc ? B - f0 : bc;
+    const int64_t nb = std::min(B - f0, bc);
     const uint8_t* src = frames + f0 * H * W * 3;
     uint8_t* tmp = (uint8_t*)ws + f0 * t.rows * n * 3;
-    char* dst = (char*)out + f0 * 3 * n * n * (out_bf16 ? 2 : 4);
+    void* dst = (char*)out + f0 * 3 * n * n * (out_bf16 ? 2 : 4);
     const int64_t th = nb * t.rows * n;
-    hipLaunchKernelGGL(resample_h_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, s, src, tmp, t.kh,
-                       t.bh, t.ksh, H, W, n, t.r0, t.rows, th);
+    if ((e = launch_kernel(resample_h_kernel, dim3((unsigned)((th + 255) / 256)), 256, s, src, tmp, t.kh, t.bh, t.ksh,
+                           H, W, n, t.r0, t.rows, th)) != hipSuccess)
+      return e;
     const int64_t tv = nb * n * n;
-    if (out_bf16)
-      hipLaunchKernelGGL(resample_v_kernel<true>, dim3((unsigned)((tv + 255) / 256)), dim3(256), 0, s, tmp, dst,
-                         t.kv, t.bv, t.ksv, t.rows, n, t.r0, nm, tv);
-    else
-      hipLaunchKernelGGL(resample_v_kernel<false>, dim3((unsigned)((tv + 255) / 256)), dim3(256), 0, s, tmp, dst,
-                         t.kv, t.bv, t.ksv, t.rows, n, t.r0, nm, tv);
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return le;
+    e = with_value<0, 1>(out_bf16 != 0, [&](auto bf) {
+      return launch_kernel(resample_v_kernel<decltype(bf)::value != 0>, dim3((unsigned)((tv + 255) / 256)), 256, s,
+                           (const uint8_t*)tmp, dst, t.kv, t.bv, t.ksv, t.rows, n, t.r0, nm, tv);
+    });
+    if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }

@@ -128,6 +128,83 @@ static void check_gather() {
   CHECK(mi_host_gather(d, nullptr, nullptr, 0, 4) == MI_OK, "gather of nothing");
 }
 
+// mi_jpeg_workspace_bytes is the contract between the caller's allocation and mi_jpeg_decode's
+// check.  Its values over geometries x segment counts x frame counts x data sizes, recorded from
+// the library before geometry and workspace listing were merged into single functions, and
+// mi_jpeg_decode refusing a workspace one byte smaller before any device work.
+static void check_jpeg_workspace_record() {
+  struct Geo {
+    const char* name;
+    int W, H, ncomp, hs0, vs0;
+  };
+  const Geo geos[7] = {{"gray 1x1", 1, 1, 1, 1, 1},         {"gray 45x61", 45, 61, 1, 1, 1},
+                       {"4:4:4 17x9", 17, 9, 3, 1, 1},      {"4:2:2 53x37", 53, 37, 3, 2, 1},
+                       {"4:2:0 16x33", 16, 33, 3, 2, 2},    {"4:2:0 1280x720", 1280, 720, 3, 2, 2},
+                       {"4:2:0 3840x2160", 3840, 2160, 3, 2, 2}};
+  const int32_t frames[3] = {1, 3, 8192};
+  const int64_t sizes[5] = {0, 1023, 1024, 1025, (int64_t)8192 * 228000};
+  struct Rec {
+    int geo, nseg;
+    unsigned long long bytes[15];   // [frames][sizes]
+  };
+  const Rec recs[14] = {
+      {0, 1, {7168ull, 8192ull, 8448ull, 8448ull, 2398567168ull, 7936ull, 8960ull, 9216ull, 9216ull, 2398567936ull,
+              4461824ull, 4462848ull, 4462848ull, 4462848ull, 2403021824ull}},
+      {0, 5, {256ull, 256ull, 256ull, 256ull, 256ull, 768ull, 768ull, 768ull, 768ull, 768ull, 1572864ull, 1572864ull,
+              1572864ull, 1572864ull, 1572864ull}},
+      {1, 1, {16128ull, 17152ull, 17408ull, 17408ull, 2398576128ull, 34816ull, 35840ull, 36096ull, 36096ull,
+              2398594816ull, 78386432ull, 78387456ull, 78387456ull, 78387456ull, 2476946432ull}},
+      {1, 5, {9216ull, 9216ull, 9216ull, 9216ull, 9216ull, 27648ull, 27648ull, 27648ull, 27648ull, 27648ull, 75497472ull,
+              75497472ull, 75497472ull, 75497472ull, 75497472ull}},
+      {2, 1, {10496ull, 11520ull, 11776ull, 11776ull, 2398570496ull, 17664ull, 18688ull, 18944ull, 18944ull,
+              2398577664ull, 31200512ull, 31201536ull, 31201536ull, 31201536ull, 2429760512ull}},
+      {2, 5, {3584ull, 3584ull, 3584ull, 3584ull, 3584ull, 10496ull, 10496ull, 10496ull, 10496ull, 10496ull, 28311552ull,
+              28311552ull, 28311552ull, 28311552ull, 28311552ull}},
+      {3, 1, {22272ull, 23296ull, 23552ull, 23552ull, 2398582272ull, 53248ull, 54272ull, 54528ull, 54528ull,
+              2398613248ull, 128718080ull, 128719104ull, 128719104ull, 128719104ull, 2527278080ull}},
+      {3, 5, {15360ull, 15360ull, 15360ull, 15360ull, 15360ull, 46080ull, 46080ull, 46080ull, 46080ull, 46080ull,
+              125829120ull, 125829120ull, 125829120ull, 125829120ull, 125829120ull}},
+      {4, 1, {10496ull, 11520ull, 11776ull, 11776ull, 2398570496ull, 17664ull, 18688ull, 18944ull, 18944ull,
+              2398577664ull, 31200512ull, 31201536ull, 31201536ull, 31201536ull, 2429760512ull}},
+      {4, 5, {3584ull, 3584ull, 3584ull, 3584ull, 3584ull, 10496ull, 10496ull, 10496ull, 10496ull, 10496ull, 28311552ull,
+              28311552ull, 28311552ull, 28311552ull, 28311552ull}},
+      {5, 1, {4154112ull, 4155136ull, 4155392ull, 4155392ull, 2402714112ull, 12448768ull, 12449792ull, 12450048ull,
+              12450048ull, 2411008768ull, 33976751360ull, 33976752384ull, 33976752384ull, 33976752384ull, 36375311360ull}},
+      {5, 5, {4147200ull, 4147200ull, 4147200ull, 4147200ull, 4147200ull, 12441600ull, 12441600ull, 12441600ull,
+              12441600ull, 12441600ull, 33973862400ull, 33973862400ull, 33973862400ull, 33973862400ull, 33973862400ull}},
+      {6, 1, {37331712ull, 37332736ull, 37332992ull, 37332992ull, 2435891712ull, 111981568ull, 111982592ull, 111982848ull,
+              111982848ull, 2510541568ull, 305767650560ull, 305767651584ull, 305767651584ull, 305767651584ull,
+              308166210560ull}},
+      {6, 5, {37324800ull, 37324800ull, 37324800ull, 37324800ull, 37324800ull, 111974400ull, 111974400ull, 111974400ull,
+              111974400ull, 111974400ull, 305764761600ull, 305764761600ull, 305764761600ull, 305764761600ull,
+              305764761600ull}}};
+  // never read: every call below fails its argument checks first
+  const uint8_t data[8] = {0}, huff[16] = {0};
+  const uint16_t qt[64] = {0};
+  uint8_t out[4], ws[4];
+  for (const Rec& r : recs) {
+    const Geo& g = geos[r.geo];
+    // [W, H, ncomp, ri, nseg, hs0, vs0, hs1, vs1, hs2, vs2, q0, q1, q2, dc0, dc1, dc2, ac0, ac1, ac2]
+    int32_t geom[20] = {g.W, g.H, g.ncomp, r.nseg == 1 ? 0 : 1, r.nseg, g.hs0, g.vs0};
+    if (g.ncomp == 3) {
+      const int32_t rest[13] = {1, 1, 1, 1, 0, 1, 1, 0, 1, 1, 0, 1, 1};
+      std::memcpy(geom + 7, rest, sizeof rest);
+    }
+    for (int bi = 0; bi < 3; ++bi)
+      for (int si = 0; si < 5; ++si) {
+        const int32_t B = frames[bi];
+        const size_t want = (size_t)r.bytes[bi * 5 + si], got = mi_jpeg_workspace_bytes(geom, B, sizes[si]);
+        CHECK(got == want, "jpeg workspace %s nseg %d B %d data %lld: %zu, recorded %zu", g.name, r.nseg, B,
+              (long long)sizes[si], got, want);
+        std::vector<int64_t> so((size_t)B * r.nseg, 0), se((size_t)B * r.nseg, 0);
+        CHECK(mi_jpeg_decode(data, sizes[si], so.data(), se.data(), huff, nullptr, 0, qt, geom, B, out, ws, got - 1,
+                             nullptr) == MI_ERR_ARG && std::strstr(mi_last_error(), "workspace too small"),
+              "jpeg workspace %s nseg %d B %d data %lld: one byte short not refused as too small (%s)", g.name, r.nseg,
+              B, (long long)sizes[si], mi_last_error());
+      }
+  }
+}
+
 static void check_sizes() {
   const mi_clip_arch b32 = {512, 224, 12, 768, 32, 77, 49408, 512, 8, 12};
   const mi_clip_arch l14 = {768, 224, 24, 1024, 14, 77, 49408, 768, 12, 12};
@@ -166,6 +243,7 @@ static void check_sizes() {
   CHECK(mi_jpeg_workspace_bytes(geom, 8192, (int64_t)8192 * 228000) > 0, "jpeg workspace");
   CHECK(mi_jpeg_workspace_bytes(nullptr, 4, 100) == 0, "jpeg workspace of no geometry");
   CHECK(mi_jpeg_workspace_bytes(geom, -1, 100) == 0, "jpeg workspace of -1 frames");
+  check_jpeg_workspace_record();
 
   float dr = 0, da = 0;
   for (int dt = 0; dt < 2; ++dt) {

@@ -216,6 +216,33 @@ def test_chunked_entropy_matches_serial_on_corrupt_and_truncated(gpu, monkeypatc
         assert np.array_equal(g.cpu().numpy(), r), f"buffer {i}: chunked decode differs from the serial kernel"
 
 
+def test_corrupt_streams_match_record(gpu):
+    """The serial and the chunked entropy kernels share one symbol step, so the
+    test above compares that step with itself on damaged data (a run past
+    coefficient 63, a code with no match, a marker mid-scan, the zero feed after
+    a truncation).  tests/golden/jpeg_corrupt_digests.json holds what the serial
+    kernel decoded while the two steps were still written separately
+    (scripts/jpeg_corrupt_record.py): the 16 reference frames, one corrupted and
+    one truncated variant each, 225 chunks per scan.  The inputs hash as
+    recorded, and both the serial kernel and the chunked default path reproduce
+    every recorded frame."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location(
+        "jpeg_corrupt_record", os.path.join(os.path.dirname(ROOT), "scripts", "jpeg_corrupt_record.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    with open(os.path.join(ROOT, "golden", "jpeg_corrupt_digests.json")) as f:
+        want = json.load(f)
+    bufs = rec.inputs()
+    assert len(bufs) == len(want["inputs"]) == len(want["rgb"]) == 32
+    assert [rec.sha(b) for b in bufs] == want["inputs"]
+    for name, serial in (("serial", True), ("chunked", False)):
+        got = rec.decode_digests(bufs, serial=serial)
+        bad = [i for i in range(32) if got[i] != want["rgb"][i]]
+        assert not bad, f"{name} decode differs from the record on buffers {bad}"
+
+
 @pytest.mark.parametrize("quality", [20, 75, 100])
 def test_chunked_entropy_large_frames_bit_exact(gpu, quality):
     """1080p / 4K frames (hundreds of 1-KB chunks per frame, DC prediction
