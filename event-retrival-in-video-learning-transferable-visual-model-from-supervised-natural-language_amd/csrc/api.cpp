@@ -1462,6 +1462,32 @@ int mi_rank_collapse(const void* corpus, int64_t N, int corpus_dtype, const void
   return MI_OK;
 }
 
+size_t mi_rank_exclude_workspace_bytes(int64_t N, int32_t H) {
+  if (N < 0 || H < 1 || H > 32) return 0;
+  return rank_exclude_workspace_bytes(N);
+}
+
+int mi_rank_exclude(const void* corpus, int64_t N, int64_t D, int corpus_dtype, const float* hits,
+                    const int64_t* hit_index, int32_t H, int64_t index_base, float threshold, const uint32_t* mask_in,
+                    uint32_t* mask_out, int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream) {
+  if (N < 0) return fail(MI_ERR_ARG, "mi_rank_exclude: negative size");
+  if (H < 1 || H > 32) return fail(MI_ERR_UNSUPPORTED, "mi_rank_exclude: H must be in [1, 32] (got %d)", H);
+  if (D < 32 || D % 32 || D > RANK_MAX_D)
+    return fail(MI_ERR_UNSUPPORTED, "mi_rank_exclude: D must be a multiple of 32 in [32, %d] (got %lld)", RANK_MAX_D,
+                (long long)D);
+  if (corpus_dtype != MI_F32 && corpus_dtype != MI_BF16 && corpus_dtype != MI_F16)
+    return fail(MI_ERR_ARG, "mi_rank_exclude: bad corpus dtype");
+  if (threshold != threshold) return fail(MI_ERR_ARG, "mi_rank_exclude: threshold is NaN");
+  if (!corpus || !hits || !mask_out) return fail(MI_ERR_ARG, "mi_rank_exclude: null pointer");
+  if (N == 0) return MI_OK;
+  const size_t need = rank_exclude_workspace_bytes(N);
+  if (!workspace || workspace_bytes < need)
+    return fail(MI_ERR_ARG, "mi_rank_exclude: workspace too small (%zu < %zu)", workspace_bytes, need);
+  HIP_TRY(rank_exclude(corpus, N, D, corpus_dtype, hits, hit_index, H, index_base, threshold, mask_in, mask_out,
+                       out_count, workspace, (hipStream_t)stream));
+  return MI_OK;
+}
+
 int mi_mirror_build(const void* corpus, int64_t N, int64_t D, int corpus_dtype, void* mirror, void* stream) {
   int r = check_rank_args(N, D, corpus_dtype, 1, 1, MI_NORM_L2, MI_NAN_FIRST);
   if (r) return r;

@@ -370,6 +370,13 @@ hipError_t rank_collapse(const void* c0, int64_t n0, int dt0, const void* c1, in
                          int64_t base, const float* cand_s, const int64_t* cand_i, int64_t Q, int P, int k,
                          float theta, float* out_s, int64_t* out_i, int32_t* out_c, int32_t* out_slot, void* ws,
                          hipStream_t s);
+// exclusion mask (rank_exclude.hip): mask_out = mask_in minus the visible rows similar to (or named
+// by) one of 1 <= H <= 32 hits, out_count (nullable) the removed rows per hit; N >= 1; ws: one [32]
+// int32 line per workgroup
+size_t rank_exclude_workspace_bytes(int64_t N);
+hipError_t rank_exclude(const void* corpus, int64_t N, int64_t D, int dt, const float* hits, const int64_t* hit_index,
+                        int H, int64_t base, float theta, const uint32_t* mask_in, uint32_t* mask_out,
+                        int32_t* out_count, void* ws, hipStream_t s);
 // mirrored corpus (rank_mirror.hip): fp16 unit-row mirror + certified exact re-score, k <= 16
 constexpr int MIRROR_MAX_K = 16;
 int rank_mirror_supported(int64_t D);

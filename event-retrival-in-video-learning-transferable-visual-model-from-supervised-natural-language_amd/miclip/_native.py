@@ -45,6 +45,7 @@ EXPORTS = (
     "mi_clip_kernel_events", "mi_clip_kernel_times",
     "mi_rank_filtered_workspace_bytes", "mi_rank_topk_filtered",
     "mi_rank_collapse_workspace_bytes", "mi_rank_collapse",
+    "mi_rank_exclude_workspace_bytes", "mi_rank_exclude",
 )
 
 
@@ -126,6 +127,9 @@ def _bind(path):
         "mi_rank_collapse_workspace_bytes": (SZ, [I64, I32, I64]),
         "mi_rank_collapse": (ctypes.c_int, [P, I64, ctypes.c_int, P, I64, ctypes.c_int, I64, I64, P, P, I64, I32,
                                             I32, ctypes.c_float, P, P, P, P, P, SZ, P]),
+        "mi_rank_exclude_workspace_bytes": (SZ, [I64, I32]),
+        "mi_rank_exclude": (ctypes.c_int, [P, I64, I64, ctypes.c_int, P, P, I32, I64, ctypes.c_float, P, P, P, P, SZ,
+                                           P]),
         "mi_mirror_build": (ctypes.c_int, [P, I64, I64, ctypes.c_int, P, P]),
         "mi_rank_mirror_workspace_bytes": (SZ, [I64, I64]),
         "mi_normalize_rows_f16": (ctypes.c_int, [P, I64, I64, P, P]),

@@ -26,7 +26,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import _native as N
-from .retrieval import collapse_topk, merge_topk, normalize_rows_f16, pack_row_mask, rank_topk_filtered
+from .retrieval import (collapse_topk, exclude_similar, merge_topk, normalize_rows_f16, pack_row_mask,
+                        rank_topk_filtered)
 
 SORT_MIN_QUERIES = 32   # above it the queries are sorted by range begin (the kernel skips per 32-query block)
 
@@ -144,6 +145,11 @@ class FrameLibrary:
     def _mask(self, g, allow):
         """Packed mask words of group ``g`` for ``allow`` (None: no mask)."""
         import torch
+        flags = self._flags(g, allow)
+        return None if flags is None else pack_row_mask(torch.from_numpy(flags).to(self.device))
+
+    def _flags(self, g, allow):
+        """Host bool flags [rows] of group ``g`` for ``allow`` (None: no mask)."""
         if allow is None:
             return None
         flags = np.zeros(g.rows, np.bool_)
@@ -164,9 +170,63 @@ class FrameLibrary:
                 if a.min() < 0 or a.max() >= rows:
                     raise N.MiClipError(f"FrameLibrary.search: allow[{name!r}] holds a row outside [0, {rows})")
                 flags[off + a] = True
-        return pack_row_mask(torch.from_numpy(flags).to(self.device))
+        return flags
 
-    def search(self, queries, k, video=None, allow=None, nan_policy="first", distinct=None, pool=None):
+    def _fill(self, q, s, i, count, pool_i, k, pool, theta, video, allow, nan_policy):
+        """The refill rounds of a distinct search (``rank_topk_distinct(fill=True)`` over two
+        corpora): per query left short by a full pool, one mask per non-empty group, starting
+        from ``allow`` and the query's video range; ``exclude_similar`` on each group with the
+        same gathered hit rows, the filtered pass per group, ``merge_topk`` and the two-corpus
+        ``collapse_topk`` as in round 1.  Counts add up over the groups (a row belongs to one)."""
+        import torch
+        Q = q.shape[0]
+        groups, base = [], 0
+        for g in self._groups:
+            if g.rows:
+                groups.append((g, base, self._flags(g, allow), self._ranges(g, video, Q)))
+                base += g.rows
+        second = groups[1][0].corpus() if len(groups) > 1 else None
+        state = torch.stack([(i >= 0).sum(dim=1), (pool_i[:, pool - 1] >= 0).to(torch.int64)], dim=1).tolist()
+        for qi, (have, full) in enumerate(state):   # (a host read: the rounds synchronise)
+            if not full and have < k:
+                continue   # the pool held every visible row
+            masks = []
+            for g, _, flags, rng in groups:
+                vis = np.zeros(g.rows, np.bool_)
+                vis[rng[qi, 0]:rng[qi, 1]] = True if flags is None else flags[rng[qi, 0]:rng[qi, 1]]
+                masks.append(pack_row_mask(torch.from_numpy(vis).to(self.device)))
+            new, rounds, counts = i[qi, :have], 1, []
+            while True:
+                assert rounds <= k, "FrameLibrary.search: a full pool's first candidate is always accepted"
+                vec = torch.empty((new.shape[0], self.dim), dtype=torch.float32, device=self.device)
+                for g, b, _, _ in groups:
+                    here = (new >= b) & (new < b + g.rows)
+                    vec[here] = g.corpus().index_select(0, new[here] - b).float()
+                cnt = 0
+                for (g, b, _, _), m in zip(groups, masks):
+                    cnt = cnt + exclude_similar(g.corpus(), vec, new, theta, row_mask=m, index_base=b, out=m,
+                                                count=True)[1]
+                counts.append(cnt)
+                if have >= k or not full:
+                    break
+                cand = [rank_topk_filtered(g.corpus(), q[qi:qi + 1], pool, row_mask=m, index_base=b, norm=g.norm,
+                                           nan_policy=nan_policy) for (g, b, _, _), m in zip(groups, masks)]
+                s2, i2 = cand[0] if len(cand) == 1 else merge_topk(
+                    torch.cat([c[0] for c in cand], dim=1), torch.cat([c[1] for c in cand], dim=1), pool,
+                    nan_policy=nan_policy)
+                ns, ni, _, _ = collapse_topk(groups[0][0].corpus(), s2, i2, k - have, theta, corpus2=second)
+                rounds += 1
+                got, full = torch.stack([(ni[0] >= 0).sum(), (i2[0, pool - 1] >= 0).to(torch.int64)]).tolist()
+                if got == 0:
+                    break
+                s[qi, have:have + got] = ns[0, :got]
+                i[qi, have:have + got] = ni[0, :got]
+                new = ni[0, :got]
+                have += got
+            count[qi, :have] = torch.cat(counts)
+        return s, i, count
+
+    def search(self, queries, k, video=None, allow=None, nan_policy="first", distinct=None, pool=None, fill=False):
         """Top-k frames per query over the library.
 
         ``video``: None (all videos), one name, or a length-Q list of names / None (each
@@ -180,9 +240,17 @@ class FrameLibrary:
         ``min(64, 3 k)``, k <= pool <= 64) are fetched through the same filtered pass and
         merge, then collapsed at cosine >= theta over both corpora (``collapse_topk``);
         returns (scores, video_index, row, count int32 [Q, k]), count = the pool's frames
-        collapsed into the hit, itself included (0 in unused slots)."""
+        collapsed into the hit, itself included (0 in unused slots).
+
+        ``fill=True`` (with ``distinct``): the distinct top-k of all visible frames instead of
+        the pool's, by refill rounds (``retrieval.rank_topk_distinct(fill=True)``): a query
+        that a full pool left short of k hits excludes everything similar to its hits and ranks
+        again, until k hits or no visible frame is left.  count then covers every visible
+        frame of the library.  Reads hit counts on the host between rounds."""
         import torch
         want = k
+        if fill and distinct is None:
+            raise N.MiClipError("FrameLibrary.search: fill is an option of a distinct search")
         if distinct is not None:
             pool = min(64, 3 * k) if pool is None else int(pool)
             if not 1 <= want <= pool <= 64:
@@ -236,7 +304,10 @@ class FrameLibrary:
             else:
                 # the global index runs over the non-empty groups' corpora in this order
                 second = live[1].corpus() if len(live) > 1 else None
+                pool_i = i
                 s, i, count, _ = collapse_topk(live[0].corpus(), s, i, want, distinct, corpus2=second)
+                if fill:
+                    s, i, count = self._fill(q, s, i, count, pool_i, want, pool, distinct, video, allow, nan_policy)
             vid, row = self.locate(i)
             return s, vid, row, count
         vid, row = self.locate(i)

@@ -220,25 +220,155 @@ def collapse_topk(corpus, cand_scores, cand_index, k, threshold, index_base=0, c
     return out_s, out_i, out_c, out_slot
 
 
-def rank_topk_distinct(corpus, queries, k, threshold, pool=None, **rank_kwargs):
+EXCLUDE_H = 32      # hits per mi_rank_exclude call (one 32-column MFMA block)
+
+
+def exclude_similar(corpus, hits, hit_index=None, threshold=0.9, row_mask=None, index_base=0, out=None, count=False):
+    """Remove from a row mask every visible row similar to one of ``hits`` (``mi_rank_exclude``,
+    csrc/rank_exclude.hip): one streaming pass over ``corpus`` [N, D] (device).
+
+    ``hits`` [H, D]: the hits' stored rows (any dtype, moved to the device and widened with
+    ``.float()``); ``hit_index`` int64 [H] or None: their global indices, so that a zero-norm hit
+    removes its own row (an index outside ``[index_base, index_base + N)`` names no row).
+    ``row_mask``: None (every row visible), a bool tensor [N] or packed int32 / uint32 words, as
+    ``rank_topk_filtered`` takes it.  A visible row is removed when its cosine (``collapse_topk``'s)
+    to some hit is >= ``threshold`` or a hit names it.  ``out``: the int32 words to write (may be
+    the packed ``row_mask`` itself: in place).  More than 32 hits run as chained calls of 32, each
+    on the previous call's mask.
+
+    Returns (mask int32 [(N + 31) // 32], count int32 [H] or None) on the device; with
+    ``count=True`` ``count[m]`` is the number of removed rows attributed to hit m: the lowest
+    similar slot, else the lowest slot naming the row.
+    """
+    import torch
+    if not corpus.is_cuda:
+        raise N.MiClipError("exclude_similar runs on the GPU: move the corpus to the device first")
+    c = _corpus(corpus)
+    Nrows, D = c.shape
+    h = hits if hits.dim() == 2 else hits.reshape(1, -1)
+    h = h.to(c.device).float().contiguous()
+    H = h.shape[0]
+    if h.shape[1] != D:
+        raise N.MiClipError(f"dimension mismatch: corpus D={D}, hits D={h.shape[1]}")
+    if H < 1:
+        raise N.MiClipError("exclude_similar: needs at least one hit")
+    if not (32 <= D <= MAX_D and D % 32 == 0):
+        raise N.MiClipError(f"D must be a multiple of 32 in [32, {MAX_D}], got {D}")
+    hi = None
+    if hit_index is not None:
+        hi = torch.as_tensor(hit_index).reshape(-1).to(device=c.device, dtype=torch.int64).contiguous()
+        if hi.shape[0] != H:
+            raise N.MiClipError(f"exclude_similar: {hi.shape[0]} indices for {H} hits")
+    words = (Nrows + 31) // 32
+    mask = None if row_mask is None else _row_mask(row_mask, Nrows, c.device)
+    if out is None:
+        out = torch.empty(words, dtype=torch.int32, device=c.device)
+    elif not (out.is_cuda and out.device == c.device and out.dtype == torch.int32 and out.is_contiguous()
+              and out.numel() >= words):
+        raise N.MiClipError(f"exclude_similar: out must be {words} contiguous int32 words on the corpus' device")
+    cnt = torch.zeros(H, dtype=torch.int32, device=c.device) if count else None
+    if Nrows == 0:
+        return out[:words], cnt
+    L = N.lib()
+    with torch.cuda.device(c.device):
+        ws = _workspace(c.device, L.mi_rank_exclude_workspace_bytes(Nrows, EXCLUDE_H))
+        for b in range(0, H, EXCLUDE_H):
+            n = min(EXCLUDE_H, H - b)
+            N.check(L.mi_rank_exclude(c.data_ptr(), Nrows, D, N.dtype_code(c.dtype), h[b:b + n].data_ptr(),
+                                      hi[b:b + n].data_ptr() if hi is not None else None, n, int(index_base),
+                                      float(threshold), mask.data_ptr() if mask is not None else None,
+                                      out.data_ptr(), cnt[b:b + n].data_ptr() if count else None,
+                                      ws.data_ptr(), ws.numel(), N.stream_ptr(c.device)), "mi_rank_exclude")
+            mask = out
+    return out[:words], cnt
+
+
+def _pool_candidates(corpus, queries, pool, mask, rank_kwargs):
+    """[Q, pool] ranked candidates of ``rank_topk`` (or, under a mask, ``rank_topk_filtered``),
+    padded with empty slots when the corpus holds fewer rows."""
+    import torch
+    if mask is None:
+        s, i = rank_topk(corpus, queries, pool, **rank_kwargs)
+    else:
+        s, i = rank_topk_filtered(corpus, queries, pool, row_mask=mask, **rank_kwargs)
+    if s.shape[1] < pool:
+        pad = pool - s.shape[1]
+        s = torch.cat([s, s.new_full((s.shape[0], pad), float("-inf"))], dim=1)
+        i = torch.cat([i, i.new_full((i.shape[0], pad), -1)], dim=1)
+    return s, i
+
+
+def rank_topk_distinct(corpus, queries, k, threshold, pool=None, fill=False, row_mask=None, **rank_kwargs):
     """Top-k distinct rows: ``rank_topk`` for ``pool`` candidates (default ``min(64, 3 k)``, the
     reference's ``top_k * 3`` over-fetch, clipped to the row count), then ``collapse_topk`` at
     ``threshold``.  ``rank_kwargs`` go to ``rank_topk`` (index_base, norm, nan_policy).
+    ``row_mask`` (bool [N] or packed words): only these rows are visible; the pool then comes
+    from ``rank_topk_filtered``.
     Returns ``collapse_topk``'s (scores, index, count, slot); hit slots beyond the distinct
-    rows the pool holds are (-inf, -1, 0)."""
+    rows the pool holds are (-inf, -1, 0).
+
+    ``fill=True``: the distinct top-k of ALL visible rows (the greedy walk of the whole ranking,
+    tests/exclude_ref.py ``fill_ref``) instead of the pool's.  Round 1 is the path above.  A
+    query left with fewer than k hits by a full pool goes on alone: ``exclude_similar`` removes
+    every row similar to its new hits from its mask, ``rank_topk_filtered`` ranks ``pool`` rows
+    under the mask, ``collapse_topk`` fills the remaining slots, until k hits or a short pool
+    (the visible rows are exhausted); at most k rounds, each a full pool's first candidate at
+    least.  Returns (scores, index, count): a query that had k hits keeps its scores (bit for
+    bit) and indices, ``count`` is the number of visible corpus rows in the hit's group, itself
+    included, and there is no ``slot`` (no single pool to refer to).  Cost: the corpus-wide
+    counts take one ``exclude_similar`` pass over the corpus per query and round's hits, so a
+    query whose pool already gave k hits pays one pass too, and Q queries run at least Q passes
+    one after another; the only query that costs nothing extra is one whose short pool held every
+    visible row (fewer than k hits, nothing left to rank: its pool counts are the corpus').  The rounds read hit counts on the host: ``fill=True``
+    synchronises and cannot be captured in a graph.
+    """
+    import torch
     if not 1 <= k <= REG_K:
         raise N.MiClipError(f"rank_topk_distinct: k must be in [1, {REG_K}]")
     pool = min(REG_K, 3 * k) if pool is None else int(pool)
     if not k <= pool <= REG_K:
         raise N.MiClipError(f"rank_topk_distinct: pool must be in [k, {REG_K}] (got {pool})")
-    pool = max(min(pool, corpus.shape[0]), k)   # rank_topk pads to k columns only when k > N
-    s, i = rank_topk(corpus, queries, pool, **rank_kwargs)
-    if s.shape[1] < k:   # fewer rows than k: the pool is every row, padded with empty slots
-        import torch
-        pad = k - s.shape[1]
-        s = torch.cat([s, s.new_full((s.shape[0], pad), float("-inf"))], dim=1)
-        i = torch.cat([i, i.new_full((i.shape[0], pad), -1)], dim=1)
-    return collapse_topk(corpus, s, i, k, threshold, index_base=rank_kwargs.get("index_base", 0))
+    Nrows = corpus.shape[0]
+    pool = max(min(pool, Nrows), k)   # rank_topk pads to k columns only when k > N
+    base = rank_kwargs.get("index_base", 0)
+    mask0 = None if row_mask is None else _row_mask(row_mask, Nrows, corpus.device)
+    s, i = _pool_candidates(corpus, queries, pool, mask0, rank_kwargs)
+    res = collapse_topk(corpus, s, i, k, threshold, index_base=base)
+    if not fill:
+        return res
+    out_s, out_i, out_c, _ = res
+    if Nrows == 0:
+        return out_s, out_i, out_c
+    c = _corpus(corpus)
+    q = _queries(queries, c.device)
+    fkw = {n: v for n, v in rank_kwargs.items() if n in ("norm", "nan_policy")}
+    nhit = (out_i >= 0).sum(dim=1)
+    state = torch.stack([nhit, (i[:, pool - 1] >= 0).to(nhit.dtype)], dim=1).tolist()   # host read: synchronises
+    for qi, (have, full) in enumerate(state):
+        if not full and have < k:
+            continue   # the pool held every visible row: hits and counts are the corpus' already
+        new = out_i[qi, :have]
+        mask, rounds, counts = mask0, 1, []
+        while True:
+            assert rounds <= k, "rank_topk_distinct: a full pool's first candidate is always accepted"
+            rows = c.index_select(0, new - base)
+            mask, cnt = exclude_similar(c, rows, new, threshold, row_mask=mask, index_base=base,
+                                        out=None if mask is mask0 else mask, count=True)
+            counts.append(cnt)
+            if have >= k or not full:
+                break
+            s2, i2 = rank_topk_filtered(c, q[qi:qi + 1], pool, row_mask=mask, index_base=base, **fkw)
+            ns, ni, _, _ = collapse_topk(c, s2, i2, k - have, threshold, index_base=base)
+            rounds += 1
+            got, full = torch.stack([(ni[0] >= 0).sum(), (i2[0, pool - 1] >= 0).to(torch.int64)]).tolist()
+            if got == 0:
+                break
+            out_s[qi, have:have + got] = ns[0, :got]
+            out_i[qi, have:have + got] = ni[0, :got]
+            new = ni[0, :got]
+            have += got
+        out_c[qi, :have] = torch.cat(counts)
+    return out_s, out_i, out_c
 
 
 def normalize_rows_f16(rows, out=None):

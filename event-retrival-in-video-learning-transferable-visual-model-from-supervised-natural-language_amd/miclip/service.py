@@ -32,7 +32,8 @@ import numpy as np
 from . import api
 from .preprocess import decode_chunk, load_frames
 from .library import FrameLibrary
-from .retrieval import MirroredCorpus, collapse_topk, normalize_rows_f16, rank_topk
+from .retrieval import (MirroredCorpus, collapse_topk, exclude_similar, normalize_rows_f16, rank_topk,
+                        rank_topk_distinct)
 
 # corpora from this many rows on also get an fp16 ranking mirror (scripts/mirror_micro.py:
 # 1M rows 1.6-1.9x faster than the exact pass, 125k rows slower: fixed merge/re-score cost)
@@ -355,9 +356,10 @@ class EmbeddingService:
             return []
 
     # ------------------------------------------------------------- distinct
-    def _rank_distinct(self, video_name, query_vec, top_k, similarity, pool, with_groups):
+    def _rank_distinct(self, video_name, query_vec, top_k, similarity, pool, with_groups, fill=False):
         """The top-k distinct frames of one video: ``_rank`` for the pool (the mirror when it
-        applies), ``collapse_topk`` over the resident rows, then the frame mapping."""
+        applies), ``collapse_topk`` over the resident rows, then the frame mapping.
+        ``fill``: ``rank_topk_distinct(fill=True)`` over the resident rows instead."""
         import torch
         entry = self._corpus_on_device(video_name)
         if entry is None:
@@ -368,6 +370,8 @@ class EmbeddingService:
             return []
         pool = min(64, 3 * k) if pool is None else int(pool)
         pool = min(max(pool, k), 64, corpus.shape[0])
+        if fill:
+            return self._rank_distinct_filled(video_name, entry, query_vec, k, float(similarity), pool, with_groups)
         s, idx = self._rank(entry, query_vec, pool)
         s = torch.from_numpy(np.ascontiguousarray(s)).reshape(1, -1)
         idx = torch.from_numpy(np.ascontiguousarray(idx)).reshape(1, -1)
@@ -379,21 +383,54 @@ class EmbeddingService:
             return [frames[i] for i in hit if i >= 0]
         return [(frames[i], [frames[j] for j in idx[slot == s] if j != i]) for s, i in enumerate(hit) if i >= 0]
 
+    def _rank_distinct_filled(self, video_name, entry, query_vec, k, similarity, pool, with_groups):
+        """``_rank_distinct`` through the refill rounds.  A hit's group is recovered with one
+        single-hit ``exclude_similar`` per hit, chained in slot order: the bits it clears
+        (mask before XOR mask after) are the frames of the video collapsed into that hit.
+        Round 1 is ``rank_topk_distinct``'s exact pass, not ``_rank``: a video large enough for
+        the fp16 mirror (certified, so the same result) pays the slower pool pass here."""
+        import torch
+        corpus, norm = entry
+        q = torch.as_tensor(np.asarray(query_vec, dtype=np.float32).reshape(1, -1), device=corpus.device)
+        _, hit, _ = rank_topk_distinct(corpus, q, k, similarity, pool=pool, fill=True, norm=norm, nan_policy="first")
+        hit = [i for i in hit[0].tolist() if i >= 0]   # one host read
+        frames = self._frames(video_name)
+        if not with_groups:
+            return [frames[i] for i in hit]
+        n = corpus.shape[0]
+        mask, masks = None, []
+        for i in hit:
+            mask, _ = exclude_similar(corpus, corpus[i:i + 1], [i], similarity, row_mask=mask)
+            masks.append(mask)
+        prev = np.full((n + 31) // 32, -1, np.int32)
+        out = []
+        for i, m in zip(hit, torch.stack(masks).cpu().numpy()):
+            gone = np.unpackbits((prev ^ m).view(np.uint8), bitorder="little")[:n]
+            out.append((frames[i], [frames[j] for j in np.flatnonzero(gone) if j != i]))
+            prev = m
+        return out
+
     def search_top_frames_distinct(self, query, top_k, video_name=None, similarity=0.9, pool=None,
-                                   with_groups=False):
+                                   with_groups=False, fill=False):
         """``search_top_frames`` for distinct moments: the best ``pool`` frames (default
         ``min(64, 3 top_k)``, the reference's ``top_k * 3`` over-fetch) collapsed where the
         cosine of two stored rows is >= ``similarity``; at most ``top_k`` <= 64 frames, best
         first, each the best-ranked of its group.  ``with_groups=True``: ``[(frame, [the
         pool's frames collapsed into it]), ...]``.  Same caching, frame mapping and
-        swallow-to-``[]`` as ``search_top_frames``."""
+        swallow-to-``[]`` as ``search_top_frames``.
+        ``fill=True``: the distinct top-k of the whole video instead of the pool's
+        (``rank_topk_distinct(fill=True)``): ``top_k`` frames whenever the video holds that many
+        distinct ones, however repetitive its footage.  A group then lists every frame of the
+        video collapsed into the hit, in frame order (not only the pool's, in rank order)."""
         try:
             cache_key = f"search_distinct_{self.active_model}_{query}_{top_k}_{similarity}_{pool}_{bool(with_groups)}"
+            if fill:
+                cache_key += "_fill"
             cached = self.cache_service.get_search_results(cache_key, video_name)
             if cached is not None:
                 return cached
             text_features = self.get_text_features(query, video_name)
-            out = self._rank_distinct(video_name, text_features, top_k, similarity, pool, with_groups)
+            out = self._rank_distinct(video_name, text_features, top_k, similarity, pool, with_groups, fill)
             if out is None:
                 return []
             self.cache_service.set_search_results(cache_key, video_name, out)
@@ -403,12 +440,12 @@ class EmbeddingService:
             return []
 
     def search_top_frames_by_image_distinct(self, image_features, top_k, video_name=None, similarity=0.9, pool=None,
-                                            with_groups=False):
+                                            with_groups=False, fill=False):
         """``search_top_frames_by_image`` with the collapse of ``search_top_frames_distinct``
-        (not cached, as ``search_top_frames_by_image``)."""
+        (``fill`` included; not cached, as ``search_top_frames_by_image``)."""
         try:
             out = self._rank_distinct(video_name, np.asarray(image_features, dtype=np.float32).reshape(-1), top_k,
-                                      similarity, pool, with_groups)
+                                      similarity, pool, with_groups, fill)
             return [] if out is None else out
         except Exception as e:
             print(f"Error in search_top_frames_by_image_distinct: {e}")

@@ -221,6 +221,46 @@ int mi_rank_collapse(const void* corpus, int64_t N, int corpus_dtype,
                      float* out_scores, int64_t* out_index, int32_t* out_count, int32_t* out_slot,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* Workspace bytes mi_rank_exclude needs for (N, H): one [32] int32 line per
+ * workgroup of the pass; 0 for N < 0 or H outside [1, 32]. */
+size_t mi_rank_exclude_workspace_bytes(int64_t N, int32_t H);
+
+/* Exclusion mask: one streaming pass over the corpus that removes from a row
+ * mask every visible row similar to one of H hits, the step that lets distinct
+ * top-k refill a pool with fewer than k distinct frames (rank a pool,
+ * mi_rank_collapse it, exclude what is similar to the accepted hits,
+ * mi_rank_topk_filtered again under the new mask).
+ * sim(a, b) is mi_rank_collapse's: dot(a,b) / (|a| |b|) of the stored rows
+ * widened exactly to f32, all three sums in f32 on the exact-f32 MFMA (error
+ * against float64 <= 2 D 2^-24 plus a few ulps); a row or hit whose sum of
+ * squares is zero or not finite is similar to nothing; sim >= threshold is
+ * false for NaN.
+ * corpus: device [N,D] (MI_F32 / MI_BF16 / MI_F16, row stride D), 32 <= D <=
+ * 1024, D % 32 == 0.  hits: device f32 [H,D], the hits' stored rows widened;
+ * hit_index: device int64 [H], the hits' global indices, or NULL; 1 <= H <= 32.
+ * Masks are mi_rank_topk_filtered's: bit r & 31 of word r >> 5, (N+31)/32
+ * words; mask_in NULL = every row visible; mask_out may alias mask_in.
+ * Row r is removed when it is visible in mask_in and (sim(r, hit_m) >=
+ * threshold for some m, or hit_index[m] - index_base == r for some m: a
+ * zero-norm hit removes its own row).  mask_out bit = mask_in bit and not
+ * removed; bits of rows >= N in the last word are written 0.
+ * out_count: device int32 [H] or NULL; out_count[m] = removed rows attributed
+ * to slot m: a removed row goes to the lowest m with sim >= threshold, else to
+ * the lowest m whose hit_index names it.  An entry of hit_index outside
+ * [index_base, index_base + N) names no row (a hit may live in another
+ * corpus).  For more than 32 hits chain calls, each taking the previous
+ * mask_out as its mask_in: rows similar to earlier slots are then invisible,
+ * so lowest-slot attribution holds across the calls.
+ * 32-row tiles whose mask_in word is 0 are neither loaded nor scored.  The
+ * counts are summed without atomics (deterministic).  All arrays are read by
+ * the kernels: no synchronisation, no allocation, capturable.  N = 0 returns
+ * MI_OK and writes nothing. */
+int mi_rank_exclude(const void* corpus, int64_t N, int64_t D, int corpus_dtype,
+                    const float* hits, const int64_t* hit_index, int32_t H,
+                    int64_t index_base, float threshold,
+                    const uint32_t* mask_in, uint32_t* mask_out, int32_t* out_count,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* Ranking mirror of a corpus for mi_rank_mirror (an
  * HBM-resident half-width mirror beside the f32 master of
  * EmbeddingService.get_embeddings, embedding_service.py:186-217).
