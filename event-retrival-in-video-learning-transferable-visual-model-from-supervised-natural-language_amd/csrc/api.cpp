@@ -1488,6 +1488,31 @@ int mi_rank_exclude(const void* corpus, int64_t N, int64_t D, int corpus_dtype, 
   return MI_OK;
 }
 
+size_t mi_event_workspace_bytes(int64_t N, int64_t Q, int32_t k) {
+  if (N < 0 || Q < 0 || k < 1 || k > RANK_REG_K || !event_sizes_ok(N, Q)) return 0;
+  return event_workspace_bytes(N, Q, k);
+}
+
+int mi_event_topk(const float* scores, int64_t N, int64_t Q, const float* threshold, const int64_t* row_time,
+                  const uint32_t* row_mask, const int64_t* query_range, int64_t max_gap, int32_t min_count, int32_t k,
+                  int64_t index_base, float* out_score, int64_t* out_peak, int64_t* out_begin, int64_t* out_end,
+                  int32_t* out_count, int32_t* out_total, void* workspace, size_t workspace_bytes, void* stream) {
+  if (N < 0 || Q < 0) return fail(MI_ERR_ARG, "mi_event_topk: negative size");
+  if (k < 1 || k > RANK_REG_K) return fail(MI_ERR_ARG, "mi_event_topk: k must be in [1, %d] (got %d)", RANK_REG_K, k);
+  if (max_gap < 0) return fail(MI_ERR_ARG, "mi_event_topk: max_gap must be >= 0");
+  if (min_count < 1) return fail(MI_ERR_ARG, "mi_event_topk: min_count must be >= 1 (got %d)", min_count);
+  if (!event_sizes_ok(N, Q)) return fail(MI_ERR_UNSUPPORTED, "mi_event_topk: N >= 2^31 or too many queries per call");
+  if (Q == 0) return MI_OK;
+  if (!out_score || !out_peak || !out_begin || !out_end || !out_count || !out_total || !threshold || (N > 0 && !scores))
+    return fail(MI_ERR_ARG, "mi_event_topk: null pointer");
+  const size_t need = N > 0 ? event_workspace_bytes(N, Q, k) : 0;
+  if (need && (!workspace || workspace_bytes < need))
+    return fail(MI_ERR_ARG, "mi_event_topk: workspace too small (%zu < %zu)", workspace_bytes, need);
+  HIP_TRY(event_topk(scores, N, Q, threshold, row_time, row_mask, query_range, max_gap, min_count, k, index_base,
+                     out_score, out_peak, out_begin, out_end, out_count, out_total, workspace, (hipStream_t)stream));
+  return MI_OK;
+}
+
 int mi_mirror_build(const void* corpus, int64_t N, int64_t D, int corpus_dtype, void* mirror, void* stream) {
   int r = check_rank_args(N, D, corpus_dtype, 1, 1, MI_NORM_L2, MI_NAN_FIRST);
   if (r) return r;

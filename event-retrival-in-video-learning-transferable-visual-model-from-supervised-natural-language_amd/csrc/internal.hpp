@@ -370,6 +370,16 @@ hipError_t rank_collapse(const void* c0, int64_t n0, int dt0, const void* c1, in
                          int64_t base, const float* cand_s, const int64_t* cand_i, int64_t Q, int P, int k,
                          float theta, float* out_s, int64_t* out_i, int32_t* out_c, int32_t* out_slot, void* ws,
                          hipStream_t s);
+// event search (rank_events.hip): the top-k temporal runs of hot columns of a [Q, N] score matrix
+// (include/miclip.h mi_event_topk); event_block_cols = the columns one workgroup covers at N
+int64_t event_block_cols(int64_t N);
+size_t event_workspace_bytes(int64_t N, int64_t Q, int k);
+bool event_sizes_ok(int64_t N, int64_t Q);
+hipError_t event_topk(const float* scores, int64_t N, int64_t Q, const float* threshold, const int64_t* row_time,
+                      const uint32_t* row_mask, const int64_t* query_range, int64_t max_gap, int min_count, int k,
+                      int64_t index_base, float* out_score, int64_t* out_peak, int64_t* out_begin, int64_t* out_end,
+                      int32_t* out_count, int32_t* out_total, void* ws, hipStream_t s);
+
 // exclusion mask (rank_exclude.hip): mask_out = mask_in minus the visible rows similar to (or named
 // by) one of 1 <= H <= 32 hits, out_count (nullable) the removed rows per hit; N >= 1; ws: one [32]
 // int32 line per workgroup

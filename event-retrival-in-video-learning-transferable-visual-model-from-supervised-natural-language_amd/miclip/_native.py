@@ -46,6 +46,7 @@ EXPORTS = (
     "mi_rank_filtered_workspace_bytes", "mi_rank_topk_filtered",
     "mi_rank_collapse_workspace_bytes", "mi_rank_collapse",
     "mi_rank_exclude_workspace_bytes", "mi_rank_exclude",
+    "mi_event_workspace_bytes", "mi_event_topk",
 )
 
 
@@ -130,6 +131,9 @@ def _bind(path):
         "mi_rank_exclude_workspace_bytes": (SZ, [I64, I32]),
         "mi_rank_exclude": (ctypes.c_int, [P, I64, I64, ctypes.c_int, P, P, I32, I64, ctypes.c_float, P, P, P, P, SZ,
                                            P]),
+        "mi_event_workspace_bytes": (SZ, [I64, I64, I32]),
+        "mi_event_topk": (ctypes.c_int, [P, I64, I64, P, P, P, P, I64, I32, I32, I64, P, P, P, P, P, P, P, SZ, P]),
+        "mi_debug_event_block_cols": (I64, [I64]),
         "mi_mirror_build": (ctypes.c_int, [P, I64, I64, ctypes.c_int, P, P]),
         "mi_rank_mirror_workspace_bytes": (SZ, [I64, I64]),
         "mi_normalize_rows_f16": (ctypes.c_int, [P, I64, I64, P, P]),

@@ -26,8 +26,11 @@ from __future__ import annotations
 import numpy as np
 
 from . import _native as N
-from .retrieval import (collapse_topk, exclude_similar, merge_topk, normalize_rows_f16, pack_row_mask,
-                        rank_topk_filtered)
+from .retrieval import (collapse_topk, event_topk, exclude_similar, merge_topk, normalize_rows_f16, pack_row_mask,
+                        rank_topk_filtered, score_matrix)
+
+TIME_BITS = 40          # frame times and max_gap are below 2^40; a column's time is (video ordinal << 41) + t,
+                        # so two videos' columns are more than any max_gap apart
 
 SORT_MIN_QUERIES = 32   # above it the queries are sorted by range begin (the kernel skips per 32-query block)
 
@@ -39,14 +42,39 @@ class _Group:
         self.norm = norm
         self.parts = []
         self.segments = []      # (name, offset, rows)
+        self.times = []         # per segment: None or host int64 [rows]
         self.rows = 0
         self._cat = None
+        self._order = None
 
-    def append(self, name, t):
+    def append(self, name, t, times=None):
         self.segments.append((name, self.rows, int(t.shape[0])))
+        self.times.append(times)
         self.parts.append(t)
         self.rows += int(t.shape[0])
         self._cat = None
+        self._order = None
+
+    def time_order(self):
+        """(perm, col_time, gather): column c of the group's time-ordered score matrix is stored
+        row perm[c] (a stable sort by time within each video, videos stay contiguous); col_time[c]
+        = (video ordinal << 41) + t, a video without times using its row number; gather = some
+        video's times are not already sorted (perm is not the identity).  Host int64 arrays."""
+        if self._order is None:
+            perm = np.arange(self.rows, dtype=np.int64)
+            col_time = np.zeros(self.rows, np.int64)
+            gather = False
+            for ordinal, ((_, off, rows), t) in enumerate(zip(self.segments, self.times)):
+                if t is None:
+                    t = np.arange(rows, dtype=np.int64)
+                elif rows > 1 and (t[1:] < t[:-1]).any():
+                    order = np.argsort(t, kind="stable")
+                    perm[off:off + rows] = off + order
+                    t = t[order]
+                    gather = True
+                col_time[off:off + rows] = (np.int64(ordinal) << (TIME_BITS + 1)) + t
+            self._order = (perm, col_time, gather)
+        return self._order
 
     def corpus(self):
         import torch
@@ -70,9 +98,11 @@ class FrameLibrary:
         self.dim = None
 
     # ------------------------------------------------------------------ build
-    def add(self, name, rows):
+    def add(self, name, rows, times=None):
         """Append a video's embedding rows [n, D] (NumPy or torch; f32 or float16,
-        anything else is ranked as f32)."""
+        anything else is ranked as f32).  ``times``: optional integers [n], 0 <= t < 2^40, in
+        any order: the rows' positions on the video's time axis (frame numbers), used by
+        ``search_events`` only; storage and every other search are unchanged."""
         import torch
         if name in self.names:
             raise N.MiClipError(f"FrameLibrary: video {name!r} was already added")
@@ -83,13 +113,20 @@ class FrameLibrary:
             raise N.MiClipError(f"FrameLibrary.add: D = {t.shape[1]}, the library holds D = {self.dim}")
         if t.dtype not in (torch.float32, torch.float16):
             t = t.to(torch.float32)
+        if times is not None:
+            tm = np.asarray(times)
+            if tm.shape != (t.shape[0],) or (tm.size and tm.dtype.kind not in "iu"):
+                raise N.MiClipError(f"FrameLibrary.add: times must be {t.shape[0]} integers")
+            times = tm.astype(np.int64)
+            if times.size and (times.min() < 0 or times.max() >= 1 << TIME_BITS):
+                raise N.MiClipError(f"FrameLibrary.add: times must be in [0, 2^{TIME_BITS})")
         t = t.to(self.device).contiguous()
         if t.dtype == torch.float16:
             if t.shape[0]:
                 t = normalize_rows_f16(t, out=t)
-            self._groups[1].append(name, t)
+            self._groups[1].append(name, t, times)
         else:
-            self._groups[0].append(name, t)
+            self._groups[0].append(name, t, times)
         self.dim = int(t.shape[1])
         self.names.append(name)
 
@@ -312,3 +349,69 @@ class FrameLibrary:
             return s, vid, row, count
         vid, row = self.locate(i)
         return s, vid, row
+
+    def search_events(self, queries, k, threshold, max_gap, min_count=1, video=None, allow=None):
+        """Top-k events per query over the library (``retrieval.event_topk``): the runs of frames
+        scoring >= ``threshold`` whose consecutive times differ by at most ``max_gap`` (in the
+        units of ``add``'s ``times``; a video added without times counts its rows), with at least
+        ``min_count`` frames.  Events never cross videos.  ``video`` and ``allow`` are ``search``'s.
+
+        Per non-empty corpus: ``score_matrix`` over the resident rows, the score columns gathered
+        into time order when some video's times are not sorted, ``event_topk``; the two corpora's
+        lists are merged by (peak score descending, global begin column ascending).
+
+        Returns (score f32 [Q, k], video_index int32 [Q, k], peak_row, begin_row, end_row int64
+        [Q, k], count int32 [Q, k], total int32 [Q]): the rows are the caller's row numbers
+        inside the video of the event's best, first and last frame in time order; unused slots
+        are -inf / -1 / -1 / -1 / -1 / 0.  ``total`` counts the query's qualifying events."""
+        import torch
+        if not 0 <= int(max_gap) < 1 << TIME_BITS:
+            raise N.MiClipError(f"FrameLibrary.search_events: max_gap must be in [0, 2^{TIME_BITS})")
+        q = torch.as_tensor(queries)
+        q = (q if q.dim() == 2 else q.reshape(1, -1)).to(device=self.device, dtype=torch.float32)
+        Q = q.shape[0]
+        if allow is not None:
+            unknown = [n for n in allow if n not in self.names]
+            if unknown:
+                raise N.MiClipError(f"FrameLibrary.search_events: unknown video {unknown[0]!r} in allow")
+        found, col2idx, base = [], [], 0
+        for g in self._groups:
+            if g.rows == 0:
+                continue
+            perm, col_time, gather = g.time_order()
+            rng = self._ranges(g, video, Q)          # a video's columns are its rows' range
+            flags = self._flags(g, allow)
+            scores = score_matrix(g.corpus(), q, norm=g.norm)
+            perm_dev = torch.from_numpy(perm).to(self.device)
+            if gather:
+                scores = scores.index_select(1, perm_dev)
+                flags = None if flags is None else flags[perm]
+            mask = None if flags is None else pack_row_mask(torch.from_numpy(flags).to(self.device))
+            found.append(event_topk(scores, threshold, k, max_gap=max_gap, min_count=min_count,
+                                    row_time=torch.from_numpy(col_time).to(self.device), row_mask=mask,
+                                    query_range=torch.from_numpy(rng).to(self.device), index_base=base))
+            col2idx.append(perm_dev + base)
+            base += g.rows
+        if not found:
+            neg = torch.full((Q, k), -1, dtype=torch.int64, device=self.device)
+            return (torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device), neg.to(torch.int32),
+                    neg, neg.clone(), neg.clone(), torch.zeros((Q, k), dtype=torch.int32, device=self.device),
+                    torch.zeros(Q, dtype=torch.int32, device=self.device))
+        if len(found) == 1:
+            s, peak, begin, end, count, total = found[0]
+        else:
+            cat = [torch.cat([f[j] for f in found], dim=1) for j in range(5)]
+            s, begin = merge_topk(cat[0], cat[2], k)
+            # begin is unique among a query's events: the payload is gathered by it (an empty slot
+            # finds an empty slot)
+            src = (cat[2].unsqueeze(1) == begin.unsqueeze(2)).to(torch.int8).argmax(dim=2)
+            peak, end, count = (cat[j].gather(1, src) for j in (1, 3, 4))
+            total = found[0][5] + found[1][5]
+        col2idx = torch.cat(col2idx)
+
+        def rows_of(col):
+            safe = torch.where(col >= 0, col, torch.zeros_like(col))
+            return self.locate(torch.where(col >= 0, col2idx[safe], col))
+
+        vid, begin_row = rows_of(begin)
+        return s, vid, rows_of(peak)[1], begin_row, rows_of(end)[1], count, total

@@ -431,6 +431,87 @@ def rank_of_targets(scores, pair_query, pair_target):
     return out
 
 
+def event_block_cols(n):
+    """Columns one workgroup of ``mi_event_topk`` covers at ``n`` columns (introspection, for
+    tests that place events on workgroup boundaries)."""
+    return int(N.lib().mi_debug_event_block_cols(int(n)))
+
+
+def event_topk(scores, threshold, k, max_gap=0, min_count=1, row_time=None, row_mask=None, query_range=None,
+               index_base=0):
+    """Top-k temporal runs of matching frames per query (``mi_event_topk``, csrc/rank_events.hip).
+
+    ``scores``: device f32 [Q, N], columns in time order (``score_matrix``'s output).
+    ``threshold``: a number or [Q].  Column t is hot for q iff it is visible and
+    ``scores[q, t] >= threshold[q]`` (false for NaN).  ``row_time``: int64 [N], non-decreasing
+    (checked here on the host when given as a host array or list; a device tensor is trusted), or
+    None: time = column.  Consecutive hot columns whose times differ by at most ``max_gap`` chain
+    into one event; an event qualifies with at least ``min_count`` hot columns.  ``row_mask`` (bool
+    [N] or packed words) and ``query_range`` ([Q, 2] or one pair, in columns) are
+    ``rank_topk_filtered``'s.  1 <= k <= 64.
+
+    Returns (score f32, peak int64, begin int64, end int64, count int32, each [Q, k], total int32
+    [Q]) on the device: the qualifying events by peak score descending, then begin ascending;
+    peak / begin / end are ``index_base`` + column (end inclusive); unused slots are
+    -inf / -1 / -1 / -1 / 0; ``total`` counts the query's qualifying events whatever k.
+    """
+    import torch
+    if not scores.is_cuda:
+        raise N.MiClipError("event_topk runs on the GPU: the scores must be on the device")
+    if scores.dim() != 2:
+        raise N.MiClipError("event_topk: scores must be [Q, N]")
+    s = scores.to(torch.float32).contiguous()
+    Q, n = s.shape
+    dev = s.device
+    if not 1 <= k <= REG_K:
+        raise N.MiClipError(f"event_topk: k must be in [1, {REG_K}]")
+    if int(max_gap) < 0 or int(min_count) < 1:
+        raise N.MiClipError("event_topk: needs max_gap >= 0 and min_count >= 1")
+    tau = torch.as_tensor(threshold, dtype=torch.float32).reshape(-1).to(dev)
+    tau = (tau.expand(Q) if tau.numel() == 1 else tau).contiguous()
+    if tau.shape != (Q,):
+        raise N.MiClipError(f"event_topk: threshold must be a number or [Q] = {Q} values, got {tuple(tau.shape)}")
+    times = None
+    if row_time is not None:
+        if not (torch.is_tensor(row_time) and row_time.is_cuda):
+            host = torch.as_tensor(row_time).to(torch.int64).reshape(-1)
+            if host.numel() > 1 and bool((host[1:] < host[:-1]).any()):
+                raise N.MiClipError("event_topk: row_time must be non-decreasing")
+            row_time = host
+        times = row_time.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        if times.numel() != n:
+            raise N.MiClipError(f"event_topk: {times.numel()} times for {n} columns")
+    mask = None if row_mask is None else _row_mask(row_mask, n, dev)
+    rng = None if query_range is None else _query_range(query_range, Q, dev)
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_p, out_b, out_e = (torch.empty((Q, k), dtype=torch.int64, device=dev) for _ in range(3))
+    out_c = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    out_t = torch.empty(Q, dtype=torch.int32, device=dev)
+    L = N.lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, L.mi_event_workspace_bytes(n, Q, k))
+        N.check(L.mi_event_topk(s.data_ptr(), n, Q, tau.data_ptr(),
+                                times.data_ptr() if times is not None else None,
+                                mask.data_ptr() if mask is not None else None,
+                                rng.data_ptr() if rng is not None else None,
+                                int(max_gap), int(min_count), int(k), int(index_base),
+                                out_s.data_ptr(), out_p.data_ptr(), out_b.data_ptr(), out_e.data_ptr(),
+                                out_c.data_ptr(), out_t.data_ptr(), ws.data_ptr(), ws.numel(),
+                                N.stream_ptr(dev)), "mi_event_topk")
+    return out_s, out_p, out_b, out_e, out_c, out_t
+
+
+def rank_events(corpus, queries, k, threshold, max_gap=0, min_count=1, row_time=None, row_mask=None,
+                query_range=None, index_base=0, norm="l2"):
+    """``score_matrix`` followed by ``event_topk``: the top-k events of each query over the rows
+    of ``corpus`` [N, D] (device), which must already be in time order.  The scores are the exact
+    f32 scores every rank kernel ranks by."""
+    if not corpus.is_cuda:
+        raise N.MiClipError("rank_events runs on the GPU: move the corpus to the device first")
+    return event_topk(score_matrix(corpus, queries, norm=norm), threshold, k, max_gap=max_gap, min_count=min_count,
+                      row_time=row_time, row_mask=row_mask, query_range=query_range, index_base=index_base)
+
+
 class MirroredCorpus:
     """HBM-resident corpus with an fp16 ranking mirror and the master kept for
     exact re-scoring (csrc/rank_mirror.hip).

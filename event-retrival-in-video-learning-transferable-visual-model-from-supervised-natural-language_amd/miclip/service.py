@@ -32,13 +32,30 @@ import numpy as np
 from . import api
 from .preprocess import decode_chunk, load_frames
 from .library import FrameLibrary
-from .retrieval import (MirroredCorpus, collapse_topk, exclude_similar, normalize_rows_f16, rank_topk,
-                        rank_topk_distinct)
+from .retrieval import (MirroredCorpus, collapse_topk, event_topk, exclude_similar, normalize_rows_f16, rank_topk,
+                        rank_topk_distinct, score_matrix)
 
 # corpora from this many rows on also get an fp16 ranking mirror (scripts/mirror_micro.py:
 # 1M rows 1.6-1.9x faster than the exact pass, 125k rows slower: fixed merge/re-score cost)
 MIRROR_MIN_ROWS = 262_144
 from .weights import load_classifier, load_state_dict
+
+
+def frame_time_order(frames):
+    """A frames list -> (times, order).  times: int64 [n], the frame numbers the reference reads
+    from the file names (``int(Path(frame_name).stem)``, query_strategies.py:74), or None when some
+    stem is not an integer (then time is the row number).  order: int64 [n], the rows in time
+    order, a stable sort (rows of equal time keep their row order); the identity without times.
+    Frame lists come string-sorted ("10152.jpg" before "2214.jpg"), so the two orders differ."""
+    n = len(frames)
+    try:
+        stems = [os.path.splitext(os.path.basename(str(f)))[0] for f in frames]
+        if not all(st.isascii() and st.isdigit() for st in stems):
+            raise ValueError
+        times = np.array([int(st) for st in stems], dtype=np.int64).reshape(n)
+    except (ValueError, OverflowError):
+        return None, np.arange(n, dtype=np.int64)
+    return times, np.argsort(times, kind="stable").astype(np.int64)
 
 
 def gemm_f32(a, w, bias=None, relu=False):
@@ -305,9 +322,29 @@ class EmbeddingService:
             return hit[3]
         lib = FrameLibrary(device=self.original_model.device)
         for v, p in zip(names, paths):
-            lib.add(v, np.load(p))
+            rows = np.load(p)
+            # frame numbers as the time axis of search_events_all, where every stem is one
+            times = frame_time_order(self._frames(v))[0]
+            if times is not None and (times.shape[0] != rows.shape[0] or (times >= 1 << 40).any()):
+                times = None
+            lib.add(v, rows, times=times)
         self._library = (names, paths, mtimes, lib)
         return lib
+
+    @staticmethod
+    def _allow_rows(frames, allow_frames):
+        """``allow_frames`` (video -> frame basenames) as ``FrameLibrary``'s allow dict (video ->
+        row numbers); None stays None."""
+        if allow_frames is None:
+            return None
+        allow = {}
+        for v, wanted in allow_frames.items():
+            if v not in frames:
+                continue
+            wanted = {os.path.basename(f) for f in wanted}
+            allow[v] = np.array([i for i, f in enumerate(frames[v]) if os.path.basename(f) in wanted],
+                                dtype=np.int64)
+        return allow
 
     def search_top_frames_all(self, query, top_k, video_names, allow_frames=None):
         """``search_top_frames`` over several videos at once (the UI's "all videos" filter,
@@ -325,15 +362,7 @@ class EmbeddingService:
             if lib is None:
                 return []
             frames = {v: self._frames(v) for v in video_names}
-            allow = None
-            if allow_frames is not None:
-                allow = {}
-                for v, wanted in allow_frames.items():
-                    if v not in frames:
-                        continue
-                    wanted = {os.path.basename(f) for f in wanted}
-                    allow[v] = np.array([i for i, f in enumerate(frames[v]) if os.path.basename(f) in wanted],
-                                        dtype=np.int64)
+            allow = self._allow_rows(frames, allow_frames)
             text_features = self.get_text_features(query, None)
             k = min(int(top_k), max(len(lib), 1))
             _, vid, row = lib.search(np.asarray(text_features, dtype=np.float32).reshape(1, -1), k, allow=allow)
@@ -450,6 +479,92 @@ class EmbeddingService:
         except Exception as e:
             print(f"Error in search_top_frames_by_image_distinct: {e}")
             return []
+
+    # --------------------------------------------------------------- events
+    @staticmethod
+    def _event_record(frames, peak, begin, end, count, score):
+        return {"frame": frames[peak], "start": frames[begin], "end": frames[end], "frames": int(count),
+                "score": float(score)}
+
+    def search_events(self, query, top_k, video_name=None, *, threshold, max_gap, min_frames=1, with_total=False):
+        """The moments of one video that match ``query``: runs of frames scoring >= ``threshold``
+        (the cosine ``extract_query_confidence`` returns; the reference's strategies keep frames
+        with ``confidence >= adaptive_threshold``, query_strategies.py:121-186) whose consecutive
+        frame numbers differ by at most ``max_gap``, with at least ``min_frames`` frames.  The
+        time axis is the frame number in the file name (``frame_time_order``); if some name is not
+        a number it is the row number.  ``threshold`` and ``max_gap`` have no defaults: the
+        reference's 0.5 is a UI value for another score scale.
+
+        Returns ``[{"frame": best frame, "start": first frame, "end": last frame, "frames": count,
+        "score": best score}, ...]``, best first, at most ``top_k`` <= 64; with
+        ``with_total=True`` ``(that list, the number of qualifying events)``.  Same caching and
+        swallow-to-``[]`` as ``search_top_frames``."""
+        empty = ([], 0) if with_total else []
+        try:
+            import torch
+            cache_key = (f"search_events_{self.active_model}_{query}_{top_k}_{float(threshold)}_{int(max_gap)}_"
+                         f"{int(min_frames)}_{bool(with_total)}")
+            cached = self.cache_service.get_search_results(cache_key, video_name)
+            if cached is not None:
+                return cached
+            text_features = self.get_text_features(query, video_name)
+            entry = self._corpus_on_device(video_name)
+            if entry is None:
+                return empty
+            corpus, norm = entry
+            k = min(int(top_k), 64)
+            if k <= 0 or corpus.shape[0] == 0:
+                return empty
+            frames = self._frames(video_name)
+            times, order = frame_time_order(frames)
+            if len(frames) != corpus.shape[0]:
+                raise ValueError(f"{len(frames)} frames for {corpus.shape[0]} embedding rows")
+            q = torch.as_tensor(np.asarray(text_features, dtype=np.float32).reshape(1, -1), device=corpus.device)
+            scores = score_matrix(corpus, q, norm=norm)
+            row_time = None
+            if times is not None:
+                scores = scores.index_select(1, torch.from_numpy(order).to(corpus.device))
+                row_time = times[order]
+            res = event_topk(scores, float(threshold), k, max_gap=int(max_gap), min_count=int(min_frames),
+                             row_time=row_time)
+            s, peak, begin, end, count = (t[0].cpu().numpy() for t in res[:5])
+            total = int(res[5][0])
+            out = [self._event_record(frames, order[p], order[b], order[e], c, v)
+                   for v, p, b, e, c in zip(s, peak, begin, end, count) if b >= 0]
+            out = (out, total) if with_total else out
+            self.cache_service.set_search_results(cache_key, video_name, out)
+            return out
+        except Exception as e:
+            print(f"Error in search_events: {e}")
+            return empty
+
+    def search_events_all(self, query, top_k, video_names, *, threshold, max_gap, min_frames=1, allow_frames=None,
+                          with_total=False):
+        """``search_events`` over several videos at once, from the resident library
+        (``FrameLibrary.search_events``): ``[(video_name, record), ...]``, best first; events never
+        cross videos.  A video whose frame names are all numbers is on the frame-number axis, any
+        other on its row numbers.  ``allow_frames`` is ``search_top_frames_all``'s.  Not cached;
+        errors are swallowed to ``[]``."""
+        empty = ([], 0) if with_total else []
+        try:
+            video_names = list(video_names)
+            if not video_names or int(top_k) <= 0:
+                return empty
+            lib = self._frame_library(video_names)
+            if lib is None or len(lib) == 0:
+                return empty
+            frames = {v: self._frames(v) for v in video_names}
+            text_features = self.get_text_features(query, None)
+            res = lib.search_events(np.asarray(text_features, dtype=np.float32).reshape(1, -1), min(int(top_k), 64),
+                                    float(threshold), int(max_gap), min_count=int(min_frames),
+                                    allow=self._allow_rows(frames, allow_frames))
+            s, vid, peak, begin, end, count = (t[0].cpu().numpy() for t in res[:6])
+            out = [(lib.names[v], self._event_record(frames[lib.names[v]], p, b, e, c, x))
+                   for x, v, p, b, e, c in zip(s, vid, peak, begin, end, count) if v >= 0]
+            return (out, int(res[6][0])) if with_total else out
+        except Exception as e:
+            print(f"Error in search_events_all: {e}")
+            return empty
 
     # --------------------------------------------------------------- ingest
     def extract_image_embedding(self, image_path):

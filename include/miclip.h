@@ -261,6 +261,54 @@ int mi_rank_exclude(const void* corpus, int64_t N, int64_t D, int corpus_dtype,
                     const uint32_t* mask_in, uint32_t* mask_out, int32_t* out_count,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* Workspace bytes mi_event_topk needs for (N, Q, k): per query and workgroup a
+ * summary, a carried state, a count and a k-entry candidate list; positive and
+ * non-decreasing in N and Q; 0 for k outside [1, 64], negative sizes or
+ * N >= 2^31. */
+size_t mi_event_workspace_bytes(int64_t N, int64_t Q, int32_t k);
+
+/* Event search: the top-k temporal runs of matching frames per query, from a
+ * score matrix whose columns are in time order (mi_score_matrix's output, its
+ * columns gathered into time order where the rows are not).  Serves the
+ * thresholded strategies of the reference (query_strategies.py:121-186,
+ * `confidence >= adaptive_threshold`, default 0.5 at app.py:391; the
+ * `top_k * 3` over-fetch at :55, :141), which answer with frames and have no
+ * notion of time; the time axis is the frame number in the file name
+ * (`int(Path(frame_name).stem)`, query_strategies.py:74).
+ * Inputs.  scores: device f32 [Q,N], row stride N.  threshold: device f32 [Q].
+ * row_time: device int64 [N], non-decreasing (a precondition that is not
+ * checked), or NULL: time = column number.  row_mask: mi_rank_topk_filtered's
+ * packed words or NULL.  query_range: device int64 [Q][2] in columns, clipped
+ * to [0, N), or NULL.  max_gap >= 0 in the units of row_time; min_count >= 1;
+ * 1 <= k <= 64.
+ * Column t is HOT for q iff it is visible (mask bit set and inside the range)
+ * and scores[q][t] >= threshold[q]; the comparison is false for a NaN score or
+ * a NaN threshold; threshold = -inf makes every visible non-NaN column hot.
+ * Two hot columns a < b with no hot column between them are LINKED iff
+ * time[b] - time[a] <= max_gap; cold and invisible columns between them do not
+ * matter.  An EVENT is a maximal chain of linked hot columns (NULL times:
+ * max_gap = 0 makes every hot column its own event, max_gap = 1 joins adjacent
+ * hot columns only).  Its record: begin and end (first and last hot column,
+ * inclusive), count (its hot columns), peak (its largest score, bits copied),
+ * peak_col (the lowest column attaining the peak).  It QUALIFIES iff count >=
+ * min_count.
+ * Outputs.  out_score f32, out_peak / out_begin / out_end int64 (index_base +
+ * column), out_count int32, each [Q,k]: the qualifying events by peak
+ * descending (the ranking's score order, -0 = +0), then begin ascending; unused
+ * slots -inf / -1 / -1 / -1 / 0.  out_total int32 [Q]: the number of qualifying
+ * events of the query, whatever k.
+ * An event may span every workgroup of the query; no workgroup waits for
+ * another inside a launch (what crosses workgroups is carried between
+ * launches).  No atomics (deterministic), no allocation, no synchronisation:
+ * all arrays are read by the kernels, capturable.  Q = 0 or N = 0 returns
+ * MI_OK; N = 0 writes the empty slots and zero totals.  N < 2^31. */
+int mi_event_topk(const float* scores, int64_t N, int64_t Q, const float* threshold,
+                  const int64_t* row_time, const uint32_t* row_mask, const int64_t* query_range,
+                  int64_t max_gap, int32_t min_count, int32_t k, int64_t index_base,
+                  float* out_score, int64_t* out_peak, int64_t* out_begin, int64_t* out_end,
+                  int32_t* out_count, int32_t* out_total,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* Ranking mirror of a corpus for mi_rank_mirror (an
  * HBM-resident half-width mirror beside the f32 master of
  * EmbeddingService.get_embeddings, embedding_service.py:186-217).
