@@ -840,6 +840,9 @@ static int gemm_residual(mi_clip* c, const uint16_t* A, int64_t lda, const uint1
 // the rows beside it).  Needs the 8-phase kernel's 256 rows (B >= 256); the compact rows live in
 // the qkv buffer, dead after attention.  MICLIP_CLS_LAST=0 (A/B) runs the full block.
 static int cls_last() { return ab_env_int("MICLIP_CLS_LAST", 1) != 0; }
+// The bf16 tower's S <= 64 attention writes the CLS rows compactly itself (attention()'s cls_out);
+// MICLIP_CLS_ATT=0 (A/B): it writes the first 16-query tile into att and the CLS rows are gathered
+static bool cls_att_compact(int S) { return S <= 64 && ab_env_int("MICLIP_CLS_ATT", 1) != 0; }
 
 // The decision, one for every tower: the last layer, whole 256-row tiles of CLS rows, and the
 // tower's own precondition `pre`
@@ -891,10 +894,15 @@ static int in_proj_cls(mi_clip* c, int B, int S, int W, const float* vec, size_t
   return MI_OK;
 }
 
-static int last_block_cls(mi_clip* c, const Layer& L, int B, int S, int W, float** xpost, int64_t* post_stride,
-                          hipStream_t s) {
+// att_compact: attention has already written its CLS rows as the compact rows [B][W] at the head of
+// the att buffer (cls_att_compact), so none are gathered.  (They cannot go to cls_gather's carve of
+// the qkv buffer: the attention kernel's other workgroups are still reading it.)
+static int last_block_cls(mi_clip* c, const Layer& L, int B, int S, int W, bool att_compact, float** xpost,
+                          int64_t* post_stride, hipStream_t s) {
   ClsRows r;   // att [B][W] bf16, x [B] fp16 row slots
-  MI_TRY(cls_gather(c, B, S, W, c->att, (size_t)W * 2, nullptr, (size_t)W * 2, s, &r, xpost, post_stride));
+  MI_TRY(cls_gather(c, B, S, W, att_compact ? nullptr : c->att, (size_t)W * 2, nullptr, (size_t)W * 2, s, &r, xpost,
+                    post_stride));
+  if (att_compact) r.att = c->att;
   MI_TRY(gemm_residual(c, (const uint16_t*)r.att, W, L.w_out, L.b_out, r.x, B, W, W, s));
   GemmArgs f = ln_args(c, L.lw_fc, L.ls_fc, L.lc_fc, c->mlp, 4 * W, B, W);
   f.A = (const uint16_t*)r.x;
@@ -927,8 +935,10 @@ static int run_tower_fold(mi_clip* c, const std::vector<Layer>& layers, int B, i
     };
     if (cls) MI_TRY(in_proj_cls(c, B, S, W, c->rs, 8, &GemmArgs::rs, EPI_LN_BF16, s, in_proj));
     else HIP_TRY(gemm_bf16(in_proj(0, 3 * W, M, 1), EPI_LN_BF16, s));
-    HIP_TRY(attention(c->qkv, c->att, B, S, W, cls ? ATT_Q0_ONLY : 0, s));   // (cls: the CLS queries' tile only)
-    if (cls) return last_block_cls(c, L, B, S, W, xpost, post_stride, s);
+    // cls: the CLS queries' tile only; S <= 64: their rows alone, written as compact rows [B][W] of att
+    const bool compact = cls && cls_att_compact(S);
+    HIP_TRY(attention(c->qkv, c->att, B, S, W, cls ? ATT_Q0_ONLY : 0, s, nullptr, nullptr, compact ? c->att : nullptr, W));
+    if (cls) return last_block_cls(c, L, B, S, W, compact, xpost, post_stride, s);
     if (fuse) {
       MI_TRY(gemm_residual(c, c->att, W, L.w_out, L.b_out, c->x, M, W, W, s));
     } else {

@@ -19,6 +19,7 @@ namespace {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4n __attribute__((ext_vector_type(4)));
 
 // compile-time tile counts handed to the kernels' generic lambdas (bools travel as std::bool_constant)
 template <int V>
@@ -489,8 +490,8 @@ __global__ __launch_bounds__(512) void attention_flash_kernel(const uint16_t* __
 }
 
 #if MICLIP_AB
-// A/B variants of the S <= 64 case (B/32's 50 tokens; the default is attention_flash_kernel<1, 2, 1>
-// on 4 waves).  Timed in interleaved rounds at 10k frames (scripts/attn_micro.py,
+// A/B variants of the S <= 64 case (B/32's 50 tokens) on the flash body, whose instance
+// attention_flash_kernel<1, 2, 1> on 4 waves was the default before attention_s64_kernel below.  Timed in interleaved rounds at 10k frames (scripts/attn_micro.py,
 // profiles/r04_ai_attn_micro.log), all bit-identical: default 603 us; an occupancy target of 6 waves
 // per SIMD (72 instead of 74 VGPRs, MICLIP_ATTN_SHORT=3) 604 us; two adjacent heads per 8-wave
 // workgroup, their 128-byte qkv / output row segments together (=2) 616 us.
@@ -518,6 +519,268 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void a
   attention_flash_body<1, 2, 1, 2>(qkv, out, S, W, H, causal, q8, qs, rows_pad);
 }
 #endif
+
+// ------------------------------------------ attention, S <= 64, by workgroup shape
+// The single-chunk case of attention_flash_body (one (sequence, head) per workgroup, keys 0 .. 63 in
+// one LDS slot) with the workgroup's shape as template parameters; every query row's MFMA sequence,
+// softmax arithmetic and store conversion are that body's, so all instances are bit-identical to it.
+//   NWV  : waves per workgroup, 4 (one 16-query tile each) or 2 (tiles w and w + 2 each: the same
+//          waves per CU then belong to twice as many workgroups, each with its own item's loads out);
+//   KG   : the K fragments (A operand of S^T = K Q^T) are loaded from the qkv rows as 16-byte
+//          pieces, the way Q is, by every wave with a tile (rows >= S clamped: their scores are
+//          masked) -- no K image in LDS; otherwise K is staged row-major in 144-byte rows as in
+//          the flash body;
+//   VTR  : V stays row-major in LDS (one 16-byte store per staged piece, 8-byte unit u of key row r
+//          at u ^ (((r >> 1) & 3) << 2): attention_res_kernel's image) and the V^T fragments are
+//          read transposed by ds_read_b64_tr_b16; otherwise V is transposed by 2-byte LDS stores
+//          as in the flash body.  Either way rows >= S of the image are zeros.
+//   CLS  : the last vision block, read at its CLS rows alone (api.cpp last_block_cls): only wave 0
+//          loads Q (row 0 on every lane of the tile: a query's result depends on its own Q row
+//          alone), runs tile 0 and stores row 0, as row `sequence` of the compact bf16 rows `out`
+//          (cls_pitch elements apart); the other waves stage their K / V pieces and leave.
+//   ST   : how a tile's 16 output rows are stored (bf16 output; MX-fp8 always as 0).  0: AttnOut's 8 bytes
+//          a lane, sixteen 32-byte pieces per store instruction -- measured, these stores and not the
+//          loads were the slow part of the kernel (384 us without them, 605 with);
+//          1: 16 bytes a lane after an exchange between neighbouring lane groups, 64 contiguous bytes a
+//          row; 3: the rows through LDS (the K image, dead once every wave holds its fragments), each
+//          store instruction 8 whole 128-byte lines; 4 / 5: 1 / 3 as nontemporal stores; 2: none (A/B
+//          timing probe, wrong results).
+// LDS per workgroup: 17 920 B with K and transposed V, 8 704 / 8 192 B with V alone.
+template <int NWV, bool KG, bool VTR, bool CLS, int ST>
+__device__ __forceinline__ void attention_s64_body(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S,
+                                                   int W, int H, int causal, uint8_t* __restrict__ q8,
+                                                   uint8_t* __restrict__ qs, int64_t rows_pad, int64_t cls_pitch) {
+  static_assert(NWV == 2 || NWV == 4, "attention_s64: the four query tiles over 2 or 4 waves");
+  constexpr int NT = 4 / NWV, PP = 8 / NWV;   // tiles per wave; 16-byte staging pieces per thread (512 a chunk)
+  constexpr int KS = 72, VS = 68;             // LDS row strides (bf16) of the K image and the transposed V image
+  constexpr int KBYTES = KG ? 0 : 64 * KS * 2, VBYTES = VTR ? 64 * 128 : 64 * VS * 2;
+  __shared__ __attribute__((aligned(16))) char lds[KBYTES + VBYTES];
+  uint16_t* Ks = (uint16_t*)lds;
+  char* Vimg = lds + KBYTES;
+  uint16_t* Vs = (uint16_t*)Vimg;
+  const int item = blockIdx.x;
+  const int bseq = item / H, h = item % H;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t ld = 3 * (int64_t)W;
+  const uint16_t* qb = qkv + (int64_t)bseq * S * ld + h * 64;
+  const uint16_t* kb = qb + W;
+  const uint16_t* vb = qb + 2 * W;
+  const int nqt = CLS ? 1 : (S + 15) / 16;
+  const int fr = lane & 15, g = lane >> 4, fk = 8 * g;
+  const int kvalid = S;   // keys of the chunk < S
+
+  // ---- loads: Q fragments of this wave's tiles, K fragments (KG), K / V staging pieces
+  bf16x8 qf[NT][2], kf[4][2];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int qt = wave + NWV * t;
+    const int qrow = CLS ? 0 : min(qt * 16 + fr, S - 1);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      qf[t][s] = bf16x8{};
+      if (qt < nqt) qf[t][s] = *(const bf16x8*)(qb + (int64_t)qrow * ld + 32 * s + fk);
+    }
+  }
+  if (KG) {
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      const int krow = min(kt * 16 + fr, S - 1);
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        kf[kt][s] = bf16x8{};
+        if (wave < nqt && kt * 16 < kvalid) kf[kt][s] = *(const bf16x8*)(kb + (int64_t)krow * ld + 32 * s + fk);
+      }
+    }
+  }
+  uint4 kr[PP], vr[PP];
+#pragma unroll
+  for (int i = 0; i < PP; ++i) {
+    const int p = tid + i * 64 * NWV, r = p >> 3, ch = p & 7;
+    kr[i] = make_uint4(0, 0, 0, 0);
+    vr[i] = make_uint4(0, 0, 0, 0);
+    if (r < S) {
+      if (!KG) kr[i] = *(const uint4*)(kb + (int64_t)r * ld + ch * 8);
+      vr[i] = *(const uint4*)(vb + (int64_t)r * ld + ch * 8);
+    }
+  }
+  // ---- the pieces into the LDS images (PP * 64 * NWV = 512 pieces: key rows 0 .. 63 x 8 chunks)
+#pragma unroll
+  for (int i = 0; i < PP; ++i) {
+    const int p = tid + i * 64 * NWV, r = p >> 3, ch = p & 7;
+    if (!KG) *(uint4*)(&Ks[r * KS + ch * 8]) = kr[i];
+    if (VTR) {
+      *(uint4*)(Vimg + r * 128 + ((ch ^ (((r >> 1) & 3) << 1)) << 4)) = vr[i];
+    } else {
+      const uint16_t* vv = (const uint16_t*)&vr[i];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) Vs[(ch * 8 + e) * VS + r] = vv[e];
+    }
+  }
+  __syncthreads();
+  constexpr bool STL = ST == 3 || ST == 5;   // output rows staged in LDS (below)
+  static_assert(!STL || !KG, "attention_s64: the staged output rows take the K image's place");
+  if (!STL && wave >= nqt) return;   // (no barrier below)
+
+  if (!KG) {
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) kf[kt][s] = *(const bf16x8*)(&Ks[(kt * 16 + fr) * KS + 32 * s + fk]);
+  }
+  if (STL) {   // every wave holds its K fragments: the K image's 9216 bytes become 4 x 16 output rows of 144
+    __syncthreads();
+    if (wave >= nqt) return;
+  }
+  bf16x8 vf[4][2];
+  // transposed reads of the row-major image (attention_res_kernel's lane map): lane (fr, g) gets head
+  // dim dt * 16 + fr of keys 32 s + 4 g .. + 3 and 32 s + 16 + 4 g .. + 3, the P V MFMA's k order
+  const int vq = fr >> 2, vp = lane & 3, vx = (2 * g + (vq >> 1)) & 3;
+  const int rvb = (4 * g + vq) * 128 + vp * 8;
+  auto read_vf = [&]() {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        if (VTR) {
+          vf[dt][s] = vfrag(Vimg + 32 * s * 128 + rvb + ((dt ^ vx) << 5), 16 * 128);
+        } else {
+          const uint16_t* vrow = &Vs[(dt * 16 + fr) * VS + 32 * s + 4 * g];
+          const uint2 lo = *(const uint2*)vrow;
+          const uint2 hi = *(const uint2*)(vrow + 16);
+          vf[dt][s] = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+        }
+      }
+  };
+
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int qt = wave + NWV * t;
+    if (qt >= nqt) continue;  // wave-uniform
+    const int qrow = qt * 16 + fr;
+    float m = -INFINITY, l = 0.f;
+    f32x4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 sc[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      if (kt * 16 < kvalid) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][s], qf[t][s], acc, 0, 0, 0);
+      }
+      sc[kt] = acc;
+    }
+    // sc[kt][j]: query qrow, key kt*16 + 4g + j
+    if (kvalid < 64 || (causal && 64 > qt * 16)) {
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int key = kt * 16 + 4 * g + j;
+          if (key >= S || (causal && key > qrow)) sc[kt][j] = -INFINITY;
+        }
+    }
+    float cm = fmaxf(fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3])),
+                     fmaxf(fmaxf(sc[1][0], sc[1][1]), fmaxf(sc[1][2], sc[1][3])));
+    cm = fmaxf(cm, fmaxf(fmaxf(fmaxf(sc[2][0], sc[2][1]), fmaxf(sc[2][2], sc[2][3])),
+                         fmaxf(fmaxf(sc[3][0], sc[3][1]), fmaxf(sc[3][2], sc[3][3]))));
+    cm = group_max(cm);
+    const float cmu = cm * sl2;  // finite: the chunk holds key 0 <= every row
+    lazy_rescale(m, l, o, cmu);
+    const float mu = m;
+    float ps[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sc[kt][j] = __builtin_amdgcn_exp2f(fmaf(sc[kt][j], sl2, -mu));
+      ps[kt] = (sc[kt][0] + sc[kt][1]) + (sc[kt][2] + sc[kt][3]);
+    }
+    l += (ps[0] + ps[1]) + (ps[2] + ps[3]);
+    if (t == 0) {   // after the first softmax: K and V^T fragments are not live together before it
+      __builtin_amdgcn_sched_barrier(0);
+      read_vf();
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      if (s == 1 && kvalid <= 32) break;  // keys past round32(S): P = 0, V^T = 0
+      bf16x8 pb;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        pb[j] = (__bf16)sc[2 * s][j];
+        pb[4 + j] = (__bf16)sc[2 * s + 1][j];
+      }
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt][s], pb, o[dt], 0, 0, 0);
+    }
+    const float inv = 1.0f / group_sum(l);
+    if (CLS) {   // row 0 alone, as row bseq of the compact rows (AttnOut with one cls_pitch-wide row a sequence)
+      if (fr == 0) AttnOut{out, nullptr, nullptr, 0, bseq, 1, (int)cls_pitch, h}.row16_bf16(0, g, o, inv);
+    } else if (STL && !q8) {
+      // whole-line stores: the tile's 16 rows of packed bf16 (row16_bf16's conversion) through this wave's LDS
+      // rows (144 bytes apart: the 8-byte writes of a half wave hit disjoint banks), read back as 16-byte
+      // pieces, lane L piece L & 7 of row L >> 3 (+ 8), so one store instruction writes 8 rows of 128 bytes
+      char* os = lds + wave * (16 * 144);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+        *(uint2*)(os + fr * 144 + dt * 32 + g * 8) = make_uint2(pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv),
+                                                                pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv));
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        const int r = p * 8 + (lane >> 3), row = qt * 16 + r;
+        const u32x4n v = *(const u32x4n*)(os + r * 144 + (lane & 7) * 16);
+        u32x4n* dst = (u32x4n*)(out + ((int64_t)bseq * S + row) * W + h * 64 + (lane & 7) * 8);
+        if (row < S) {
+          if (ST == 5) __builtin_nontemporal_store(v, dst);
+          else *dst = v;
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (NT = 2: the next tile writes these rows again)
+      __builtin_amdgcn_wave_barrier();
+    } else if ((ST == 1 || ST == 4) && !q8) {
+      // 16-byte stores: the row's packed bf16 (row16_bf16's conversion) exchanged between the lane groups g and
+      // g ^ 1, so an even group holds dims 16 dt + 4 g .. + 7 of dt = 0 / 2 and an odd one dims 16 dt + 4 (g - 1)
+      // .. + 7 of dt = 1 / 3: two stores of 64 contiguous bytes a row instead of four of 32
+      uint16_t* dst = out + ((int64_t)bseq * S + qrow) * W + h * 64 + ((g & 1) ? 16 + 4 * (g - 1) : 4 * g);
+#pragma unroll
+      for (int dp = 0; dp < 2; ++dp) {
+        const f32x4 &oa = o[2 * dp], &ob = o[2 * dp + 1];
+        const auto x = __builtin_amdgcn_permlane16_swap(pack_bf16x2(oa[0] * inv, oa[1] * inv),
+                                                        pack_bf16x2(ob[0] * inv, ob[1] * inv), false, false);
+        const auto y = __builtin_amdgcn_permlane16_swap(pack_bf16x2(oa[2] * inv, oa[3] * inv),
+                                                        pack_bf16x2(ob[2] * inv, ob[3] * inv), false, false);
+        const u32x4n v = {x[0], y[0], x[1], y[1]};
+        if (qrow < S) {
+          if (ST == 4) __builtin_nontemporal_store(v, (u32x4n*)(dst + 32 * dp));
+          else *(u32x4n*)(dst + 32 * dp) = v;
+        }
+      }
+    } else if (ST == 2) {   // timing probe: no output stores (wrong results)
+      if (inv == 12345.678f) AttnOut{out, q8, qs, rows_pad, bseq, S, W, h}.store16(qrow, g, o, inv);
+    } else {
+      AttnOut{out, q8, qs, rows_pad, bseq, S, W, h}.store16(qrow, g, o, inv);
+    }
+  }
+}
+
+template <bool KG, bool VTR, bool CLS, int ST = 0>
+__global__ __launch_bounds__(256) void attention_s64_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
+                                                            int S, int W, int H, int causal, uint8_t* __restrict__ q8,
+                                                            uint8_t* __restrict__ qs, int64_t rows_pad,
+                                                            int64_t cls_pitch) {
+  attention_s64_body<4, KG, VTR, CLS, ST>(qkv, out, S, W, H, causal, q8, qs, rows_pad, cls_pitch);
+}
+// 2 waves x 2 tiles: 4 waves per SIMD asked of the register allocator (a wave's two tiles unrolled side by
+// side otherwise take 137 registers: 3 waves per SIMD, 6 workgroups per CU; at 5 per SIMD it spills)
+template <bool KG, bool VTR, bool CLS, int ST = 0>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void attention_s64w2_kernel(
+    const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int W, int H, int causal,
+    uint8_t* __restrict__ q8, uint8_t* __restrict__ qs, int64_t rows_pad, int64_t cls_pitch) {
+  attention_s64_body<2, KG, VTR, CLS, ST>(qkv, out, S, W, H, causal, q8, qs, rows_pad, cls_pitch);
+}
 
 
 // ----------------------------- attention, vision towers: K/V resident in LDS
@@ -1079,7 +1342,7 @@ template <auto KERNEL>
 using Kern = std::integral_constant<decltype(KERNEL), KERNEL>;
 
 hipError_t attention(const uint16_t* qkv, uint16_t* out, int B, int S, int W, int flags, hipStream_t s, uint8_t* q8,
-                     uint8_t* qs) {
+                     uint8_t* qs, uint16_t* cls_out, int64_t cls_pitch) {
   const int H = W / 64;
   const int items = B * H;
   if (items <= 0) return hipSuccess;
@@ -1103,18 +1366,53 @@ hipError_t attention(const uint16_t* qkv, uint16_t* out, int B, int S, int W, in
   const int64_t rows_pad = ((int64_t)B * S + 1) & ~1;   // rows of the MX scale layout (mx_scale_index)
   const size_t res_lds = 2 * (size_t)((S + 31) & ~31) * 128;   // resident kernels: the K and V images
 
-  // ---- 2. A/B only: MICLIP_ATTN_SHORT, the S <= 64 variants (described at their kernels)
-#if MICLIP_AB
+  // ---- 2. S <= 64: attention_s64_kernel in its measured shape S64_SHAPE (bit 0: 2 waves x 2 tiles instead of
+  // 4 x 1, bit 1: K fragments from global memory, bit 2: V row-major in LDS, read transposed, bits 3 up:
+  // the output store form; -1: the flash body's single-chunk instance in section 5).  cls_out: the CLS-row form,
+  // row 0 of every sequence into the compact rows (ATT_Q0_ONLY, bf16 output).  A/B: MICLIP_ATTN_SHORT, 100 + shape
+  // (+ 8 x the output store form, below), 30 for the flash body's instance, the older variants described
+  // at their kernels.
+  // Measured (scripts/attn_micro.py): 2 waves x 2 tiles, K and transposed V in LDS, whole-line
+  // nontemporal stores (shape 1 + 8 x 5); the CLS form on 4 waves.  ATT_Q0_ONLY without compact rows (A/B,
+  // MICLIP_CLS_ATT=0) stays on the flash body's instance, which stops after the first tile.
+  constexpr int S64_SHAPE = 41, S64_CLS_SHAPE = 0;
+  if (cls_out && (!q0 || S > 64 || q8 || causal || one_wave || stream)) return hipErrorInvalidValue;
   if (!one_wave && !stream && S <= 64) {
+    auto s64 = [&](auto shape) {
+      constexpr int SH = decltype(shape)::value;
+      constexpr int NWV = (SH & 1) ? 2 : 4;
+      constexpr bool KG = SH & 2, VTR = SH & 4;
+      // output stores: 0 8 bytes a lane; 1 16 bytes (64 contiguous a row); 3 whole 128-byte lines through LDS (shapes
+      // with a K image); 4 / 5: 1 / 3 nontemporal; 2: none (A/B timing probe)
+      constexpr int ST = SH >> 3;
+      auto go = [&](auto cls, uint16_t* dst, int cz) {
+        constexpr bool CLS = decltype(cls)::value;
+        constexpr int STK = CLS ? 0 : ST;   // (the CLS form stores one row on four lanes)
+        if constexpr (NWV == 2)
+          return launch_kernel(attention_s64w2_kernel<KG, VTR, CLS, STK>, items, 128, s, qkv, dst, S, W, H, cz, q8, qs,
+                               rows_pad, cls_pitch);
+        else
+          return launch_kernel(attention_s64_kernel<KG, VTR, CLS, STK>, items, 256, s, qkv, dst, S, W, H, cz, q8, qs,
+                               rows_pad, cls_pitch);
+      };
+      if (cls_out) return go(std::true_type{}, cls_out, 0);
+      return go(std::false_type{}, out, causal);   // (ATT_Q0_ONLY without compact rows: every row is computed)
+    };
+#if MICLIP_AB
     const int sw = ab_env_int("MICLIP_ATTN_SHORT", 0);
     // 5x: persistent workgroups with the next item's operands prefetched, x workgroups per CU (a bare 5: 4 per
     // CU: 128 VGPRs)
-    if (sw == 5 || sw / 10 == 5) {
+    if (!cls_out && (sw == 5 || sw / 10 == 5)) {
       const int per = sw == 5 ? 4 : sw % 10;
       const int gp = std::min(items, cu_count() * (per > 0 ? per : 5));
       return launch_kernel(attention_pipe_kernel, gp, 256, s, qkv, out, S, W, H, causal, q8, qs, rows_pad, items);
     }
-    switch (sw) {
+    if (sw >= 100)   // (16: the timing probe, shape 0 without its output stores)
+      return with_value<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 24, 25, 28, 29, 32, 33, 36, 37, 40, 41, 44,
+                        45>(sw - 100, s64);
+    if (!cls_out) switch (sw) {
+      case 30:   // the flash body's single-chunk instance on 4 waves
+        return launch_kernel(attention_flash_kernel<1, 2, 1>, items, 256, s, qkv, out, S, W, H, causal | q0, q8, qs, rows_pad);
       case 6:   // the V^T fragment reads batched
         return launch_kernel(attention_vb_kernel, items, 256, s, qkv, out, S, W, H, causal | q0, q8, qs, rows_pad);
       case 2:   // two heads per workgroup (an odd H: as 3)
@@ -1129,8 +1427,10 @@ hipError_t attention(const uint16_t* qkv, uint16_t* out, int B, int S, int W, in
         break;
       default: break;
     }
-  }
 #endif
+    if (cls_out) return s64(Int<S64_CLS_SHAPE>{});
+    if (S64_SHAPE >= 0 && !q0) return s64(Int<(S64_SHAPE >= 0 ? S64_SHAPE : S64_CLS_SHAPE)>{});
+  }
 
   // ---- 3. vision towers (257 / 577 tokens): K/V resident in LDS, no per-chunk barriers
   if (!one_wave && !stream && !causal && S > 64) {
@@ -1186,7 +1486,8 @@ hipError_t attention(const uint16_t* qkv, uint16_t* out, int B, int S, int W, in
 #endif
 
   // ---- 5. flash
-  // NT = ceil(tiles / 8) query tiles per wave on 8 waves; S <= 64: one tile on
+  // NT = ceil(tiles / 8) query tiles per wave on 8 waves; S <= 64 (here only with ATT_Q0_ONLY and no
+  // compact rows, or as the A/B baseline; section 2 otherwise): one tile on
   // each of 4 waves, single slot.  Fewer waves with fewer idle tile slots
   // measured slower (L/14 257 tokens on 6 waves x 3 tiles: 470 vs 421 us; text
   // 77 on 5 x 1: 45 vs 31 us): a workgroup lasts as long as its busiest wave

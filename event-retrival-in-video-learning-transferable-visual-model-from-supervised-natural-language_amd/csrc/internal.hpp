@@ -76,8 +76,8 @@ enum AttnFlags {
                          // resident-K/V kernels (parity tests of both paths); no effect elsewhere
   ATT_Q0_ONLY = 0x800    // only the first query tile's rows are computed and written (the last vision
                          // block, read at its CLS rows alone): honoured by the S <= 64 flash kernel
-                         // (16 rows) and by precise.hip's f32 kernels (32 rows); every other kernel
-                         // computes all rows
+                         // (16 rows; with attention()'s cls_out: row 0 alone, into compact rows) and by
+                         // precise.hip's f32 kernels (32 rows); every other kernel computes all rows
 };
 
 enum GemmEpi {
@@ -284,8 +284,11 @@ hipError_t im2col(const void* pixels, int in_bf16, uint16_t* out, int B, int R, 
                   hipStream_t s);
 // multi-head attention over qkv [B*S, 3W] bf16 -> out [B*S, W] bf16, head dim 64
 // q8 != nullptr: MX-fp8 output (one 64-k block per head) instead of bf16 out; flags: AttnFlags
+// cls_out != nullptr (ATT_Q0_ONLY, S <= 64, bf16): nothing goes to `out`; row 0 of sequence b is
+// written to cls_out + b * cls_pitch, the compact CLS rows of the last vision block
 hipError_t attention(const uint16_t* qkv, uint16_t* out, int B, int S, int W, int flags,
-                     hipStream_t s, uint8_t* q8 = nullptr, uint8_t* qs = nullptr);
+                     hipStream_t s, uint8_t* q8 = nullptr, uint8_t* qs = nullptr, uint16_t* cls_out = nullptr,
+                     int64_t cls_pitch = 0);
 // y [rows, D] f32 -> out (f32/bf16/f16), optional L2 normalisation
 hipError_t finalize_rows(const float* y, void* out, int out_dtype, int rows, int D, int l2,
                          hipStream_t s);

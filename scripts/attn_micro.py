@@ -18,6 +18,19 @@ SHAPES = [("B/32", 2000, 50, 768, 0), ("B/32c", 10000, 50, 768, 0), ("text", 256
           ("L/14c", 1667, 257, 1024, 0), ("L/14@336c", 1000, 577, 1024, 0)]
 
 
+# MICLIP_ATTN_SHORT values of the S <= 64 modes
+# attention_s64_kernel's shapes: bit 0 two waves x two tiles, bit 1 K fragments from global memory, bit 2 V read
+# transposed, + 8 x the output store form (STORES; 2 is the timing probe without stores, wrong results)
+STORES = {0: "", 1: " st16", 2: " nostore", 3: " stline", 4: " st16nt", 5: " stlinent"}
+S64_SHAPES = list(range(17)) + [24, 25, 28, 29] + list(range(32, 34)) + [36, 37, 40, 41, 44, 45]
+SHORT = {"short": "1", "short2": "2", "short3": "3", "pipe4": "54", "pipe8": "58", "vb": "6", "flash": "30",
+         **{f"s64_{i}": str(100 + i) for i in S64_SHAPES}}
+S64_KIND = {f"s64_{i}": "s64 " + ("2w" if i & 1 else "4w") + (" Kglob" if i & 2 else " Klds") + (" Vtr" if i & 4 else " Vt")
+            + STORES[i >> 3] for i in S64_SHAPES}
+# ATTN_S64=0,4,8: the shapes to time (default: all)
+S64_MODES = [f"s64_{i}" for i in (os.environ["ATTN_S64"].split(",") if os.environ.get("ATTN_S64") else S64_SHAPES)]
+
+
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     L = N.lib()
@@ -29,7 +42,9 @@ def main():
             continue
         qkv = (torch.randn(B * S, 3 * W, device=dev) * 1.5).bfloat16()
         outs = {}
-        modes = ([0, "vb"] if S <= 64 and os.environ.get("ATTN_SHORT_MODES") == "vb" else
+        # ATTN_SHORT_MODES=s64: the flash body's S <= 64 instance against attention_s64_kernel's eight shapes
+        modes = ([0, "flash"] + S64_MODES if S <= 64 and os.environ.get("ATTN_SHORT_MODES") == "s64" else
+                 [0, "vb"] if S <= 64 and os.environ.get("ATTN_SHORT_MODES") == "vb" else
                  [0, 0x100, "short", "short2", "short3", "pipe4", "pipe8", "vb"] if S <= 64 else [0, 0x100] if S <= 96
                  else [0] + [f"v{i}" for i in os.environ.get("ATTN_VARS", "4,5,6,7,8,9,10").split(",")])
         # resident-K/V kernel variants (attention.hip): v1 8 waves one tile at a time, v2 8 waves
@@ -40,9 +55,8 @@ def main():
 
         def run(mode):
             os.environ.pop("MICLIP_ATTN_SHORT", None)
-            if mode in ("short", "short2", "short3", "pipe4", "pipe8", "vb"):
-                os.environ["MICLIP_ATTN_SHORT"] = {"short": "1", "short2": "2", "short3": "3", "pipe4": "54", "pipe8": "58",
-                                                   "vb": "6"}[mode]
+            if mode in SHORT:
+                os.environ["MICLIP_ATTN_SHORT"] = SHORT[mode]
                 os.environ.pop("MICLIP_ATTN_VAR", None)
             elif isinstance(mode, str):
                 os.environ["MICLIP_ATTN_VAR"] = mode[1:]
@@ -68,8 +82,8 @@ def main():
             fl = 4.0 * B * S * S * W * (0.5 if causal else 1.0)
             by = B * S * 4 * W * 2
             d = (outs[mode].float() - outs[0].float()).abs().max().item()
-            kind = {0: "default", "v1": "res 8w x1", "v11": "res 8w x1 unsplit", "v12": "res 8w x1 split", "v13": "res 8w split first", "v14": "res 8w Q ahead", "v2": "res 8w x2", "v3": "res 16w x1", "v4": "r32 8w x2", "v5": "r32 12w", "v6": "r32 12w stag1", "v7": "r32 12w stag2", "v8": "r32 12w noload", "v9": "r32 12w noexp", "v10": "r32 12w 2-phase", "short": "res 4w (S<=64)", "short2": "flash 2 heads/wg", "short3": "flash 1h occ-6", "pipe4": "pipe 4/CU", "pipe8": "pipe 8/CU", "vb": "flash V reads batched", 0x100: "one-wave", 0x200: "flash(chunked)"}[mode]
-            print(f"{name:9s} {kind:16s} B={B} S={S} W={W}: {us:8.1f} us "
+            kind = {0: "default", "v1": "res 8w x1", "v11": "res 8w x1 unsplit", "v12": "res 8w x1 split", "v13": "res 8w split first", "v14": "res 8w Q ahead", "v2": "res 8w x2", "v3": "res 16w x1", "v4": "r32 8w x2", "v5": "r32 12w", "v6": "r32 12w stag1", "v7": "r32 12w stag2", "v8": "r32 12w noload", "v9": "r32 12w noexp", "v10": "r32 12w 2-phase", "short": "res 4w (S<=64)", "short2": "flash 2 heads/wg", "short3": "flash 1h occ-6", "pipe4": "pipe 4/CU", "pipe8": "pipe 8/CU", "vb": "flash V reads batched", "flash": "flash <1,2,1> 4w", **S64_KIND, 0x100: "one-wave", 0x200: "flash(chunked)"}[mode]
+            print(f"{name:9s} {kind:22s} B={B} S={S} W={W}: {us:8.1f} us (slowest round {max(times[mode]):8.1f}) "
                   f"{fl / us / 1e6:6.1f} TFLOP/s {by / us / 1e3:7.1f} GB/s  maxdiff {d:.3g}", flush=True)
 
 if __name__ == "__main__":
