@@ -1,7 +1,10 @@
 """The persistent MX-fp8 ping-pong (gemm_mxppp_kernel, the default since round 6) against one
 workgroup per tile (gemm_mxpp_kernel, MICLIP_MX_PERSIST=0 in the A/B build) at the configs[4]
 pass shapes (ViT-L/14@336px, 863 frames x 577 tokens = 497951 rows): random operands, HIP events,
-interleaved rounds in one process, outputs compared byte for byte.
+interleaved rounds in one process, outputs compared byte for byte.  The *_cls shapes are the four
+tower GEMMs of the CLS-row last block (863 rows: fewer tiles than CUs, so both columns run the
+per-tile kernel and their difference is the run's own spread).  Each figure is the best round; the
+bracket is the range over the rounds.
 usage: python scripts/mx_persist_micro.py [reps] [shapes,comma] [group widths,comma]
 (group widths: the persistent kernel's tile order, MICLIP_MX_NG, -1 = m-major; each also compared;
  an entry "pP:G" runs MICLIP_MX_PERSIST=P with MICLIP_MX_NG=G -- P 2 = persistent whatever K)"""
@@ -17,7 +20,10 @@ from miclip import _native as N  # noqa: E402
 
 M4 = 863 * 577
 SHAPES = {"qkv": (M4, 3072, 1024, 0), "out": (M4, 1024, 1024, 0), "fc8": (M4, 4096, 1024, 4),
-          "proj": (M4, 1024, 4096, 0), "fc8_100k": (99821, 4096, 1024, 4)}
+          "proj": (M4, 1024, 4096, 0), "fc8_100k": (99821, 4096, 1024, 4),
+          "qkv_cls": (863, 3072, 1024, 0), "out_cls": (863, 1024, 1024, 0), "fc8_cls": (863, 4096, 1024, 4),
+          "proj_cls": (863, 1024, 4096, 0)}
+ROUNDS = 3
 
 
 def main():
@@ -64,8 +70,8 @@ def main():
             run(k)
         torch.cuda.synchronize()
         same = torch.equal(outs["persistent"].view(torch.uint8), outs["per_tile"].view(torch.uint8))
-        best = {k: 1e30 for k in outs}
-        for _ in range(3):
+        times = {k: [] for k in outs}
+        for _ in range(ROUNDS):
             for k in outs:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -73,16 +79,18 @@ def main():
                     run(k)
                 e1.record()
                 torch.cuda.synchronize()
-                best[k] = min(best[k], e0.elapsed_time(e1) * 1e3 / reps)
+                times[k].append(e0.elapsed_time(e1) * 1e3 / reps)
+        best = {k: min(v) for k, v in times.items()}
+        span = {k: f"[{min(v):.1f}..{max(v):.1f}]" for k, v in times.items()}
         fl = 2.0 * M * Nn * K
-        print(f"{name:8s} M={M} N={Nn} K={K} epi={epi}: persistent {best['persistent']:8.1f} us "
+        print(f"{name:8s} M={M} N={Nn} K={K} epi={epi}: persistent {best['persistent']:8.1f} us {span['persistent']} "
               f"{fl / best['persistent'] / 1e6:7.1f} TF ({fl / best['persistent'] / 1e6 / 5000:.3f} of fp8 peak) | "
-              f"per-tile {best['per_tile']:8.1f} us {fl / best['per_tile'] / 1e6:7.1f} TF | bit-identical {same}",
+              f"per-tile {best['per_tile']:8.1f} us {span['per_tile']} {fl / best['per_tile'] / 1e6:7.1f} TF | bit-identical {same}",
               flush=True)
         for ng in ngs:
             k = f"ng{ng}"
             eq = torch.equal(outs[k].view(torch.uint8), outs["per_tile"].view(torch.uint8))
-            print(f"{name:8s}   group width {ng:>5s}: {best[k]:8.1f} us {fl / best[k] / 1e6:7.1f} TF "
+            print(f"{name:8s}   group width {ng:>5s}: {best[k]:8.1f} us {span[k]} {fl / best[k] / 1e6:7.1f} TF "
                   f"({fl / best[k] / 1e6 / 5000:.3f} of fp8 peak) | bit-identical {eq}", flush=True)
         del qa, qw, outs
 

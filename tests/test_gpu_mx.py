@@ -190,7 +190,7 @@ def test_gemm_mx_default_fp8_output_rows(gpu, M, N, K):
 def test_gemm_mx_persistent_bit_identical(gpu, monkeypatch, M, N, K, epi):
     """The persistent MX ping-pong (gemm_mxppp_kernel: one workgroup per CU, the next tile's first
     stages and bias streamed in under this tile's last stages, counted waits across the tile
-    boundary; and its lean stage loop, MICLIP_MX_PERSIST=4) against
+    boundary) against
     one workgroup per tile (gemm_mxpp_kernel, MICLIP_MX_PERSIST=0, A/B build):
     the same MFMAs in the same k order and the same epilogue arithmetic, so bf16 / GELU / f32 /
     MX-fp8 outputs (e4m3 bytes and their scales) are byte-identical -- several tiles per CU, odd M
@@ -204,7 +204,7 @@ def test_gemm_mx_persistent_bit_identical(gpu, monkeypatch, M, N, K, epi):
     qa, sa = _quant_gpu(a.to(gpu))
     qw, sw = _quant_gpu(w.to(gpu))
     outs = []
-    for lib, persist in ((N_.lib(), None), (N_.lib_ab(), "1"), (N_.lib_ab(), "0"), (N_.lib_ab(), "4")):
+    for lib, persist in ((N_.lib(), None), (N_.lib_ab(), "1"), (N_.lib_ab(), "0")):
         if persist is not None:
             monkeypatch.setenv("MICLIP_MX_PERSIST", persist)
         if epi == 4:
@@ -220,4 +220,133 @@ def test_gemm_mx_persistent_bit_identical(gpu, monkeypatch, M, N, K, epi):
     torch.cuda.synchronize()
     assert torch.equal(outs[0].view(torch.uint8), outs[1].view(torch.uint8))   # product = A/B persistent
     assert torch.equal(outs[1].view(torch.uint8), outs[2].view(torch.uint8))   # persistent = per tile
-    assert torch.equal(outs[1].view(torch.uint8), outs[3].view(torch.uint8))   # the lean stage loop (A/B)
+
+
+# ---- short K through the persistent stream.  M = 16500 is 65 m-tiles, the last one 116 rows.
+#   N = 3072 (12 n-tiles = 2 groups of 6): 780 tiles, three or four per workgroup on 256 CUs.  Replaying
+#     xcd_remap and tile_coords on the host for every M with at least 256 tiles: a group's partial tiles
+#     are the last tiles of XCD 3's and XCD 7's runs, so each is the LAST tile of its workgroup's stream
+#     (no M changes that at 12 n-tiles: the group boundary is also an XCD-run boundary).
+#   N = 4608 (18 n-tiles = 3 groups): 1170 tiles, the group boundaries fall inside XCD runs: workgroup 85
+#     walks tiles 85, 341, 597, 853, 1109, and its second one, 341, is (m-tile 64, n-tile 6): a partial
+#     tile whose stores drain with vmcnt(0), followed by three tiles whose waits count again (also
+#     workgroups 93, 101, ..., 12 in all; _partial_tile_mid_stream below is that replay).
+# K = 256 / 384 / 640 is nk = 4 / 6 / 10 stages: the next tile's first stages start at stage 1 / 3 / 7
+# of this one and the ring base rotates by 0 / 2 / 2 slots per tile.
+SHORT_M = 16500
+SHORT_KS = [256, 384, 640]
+SHORT_NS = [3072, 4608]
+
+
+def _partial_tile_mid_stream(M, N, cus, ng=6):
+    """(workgroup, position in its stream, tile) of the partial m-tiles that are not the last tile of their
+    workgroup: the persistent kernel's walk (xcd_remap, tile_coords of the csrc headers) on the host, for
+    n-tile groups of ng (ng <= 0 or >= the n-tiles: the m-major raster)."""
+    tm, tn = (M + 255) // 256, N // 256
+    nt = tm * tn
+    q, r = divmod(nt, 8)
+    hits = []
+    for wg in range(cus):
+        stream = range(wg, nt, cus)
+        for pos, v in enumerate(stream):
+            x, i = v % 8, v // 8
+            t = (x * (q + 1) if x < r else r * (q + 1) + (x - r) * q) + i
+            if ng <= 0 or ng >= tn:
+                mb = t // tn
+            else:
+                g, rr = divmod(t, tm * ng)
+                mb = rr // min(ng, tn - g * ng)
+            if mb == tm - 1 and M % 256 and pos < len(stream) - 1:
+                hits.append((wg, pos, v))
+    return hits
+
+
+@pytest.fixture(scope="module")
+def short_cases():
+    """Quantised operands of the [SHORT_M, N, K] cases, built once each and released with the module."""
+    cache = {}
+
+    def get(gpu, N, K):
+        import torch
+        if (N, K) not in cache:
+            g = torch.Generator(device="cpu").manual_seed(SHORT_M + N + K)
+            a = (torch.randn(SHORT_M, K, generator=g) * 2).bfloat16()
+            w = (torch.randn(N, K, generator=g) * K ** -0.5).bfloat16()
+            bias = torch.randn(N, generator=g).to(gpu)
+            cache[(N, K)] = _quant_gpu(a.to(gpu)) + _quant_gpu(w.to(gpu)) + (bias,)
+        return cache[(N, K)]
+
+    yield get
+    cache.clear()
+
+
+def _short_run(lib, ops, N, K, epi):
+    import torch
+    N_ = _lib()
+    qa, sa, qw, sw, bias = ops
+    M = SHORT_M
+    if epi == 4:
+        out = torch.zeros((M * N + 255) // 256 * 256 + (N // 128) * (M + (M & 1)) * 2, dtype=torch.uint8,
+                          device=qa.device)
+    else:
+        out = torch.zeros(M, N, dtype=torch.float32 if epi == 3 else torch.bfloat16, device=qa.device)
+    rc = lib.mi_op_gemm_mx(qa.data_ptr(), sa.data_ptr(), qw.data_ptr(), sw.data_ptr(), bias.data_ptr(),
+                           out.data_ptr(), M, N, K, epi, _stream())
+    if rc:
+        raise N_.MiClipError(f"gemm_mx: {lib.mi_last_error()}")
+    return out
+
+
+def test_short_k_walk_has_partial_tile_mid_stream():
+    """The host replay behind the shapes above, at the MI355X's 256 CUs."""
+    assert all(_partial_tile_mid_stream(M, 3072, 256) == [] for M in range(5400, 40000, 256))
+    hits = _partial_tile_mid_stream(SHORT_M, 4608, 256)
+    assert len(hits) == 12 and hits[0] == (85, 1, 341)
+
+
+@pytest.mark.parametrize("N", SHORT_NS)
+@pytest.mark.parametrize("K", SHORT_KS)
+@pytest.mark.parametrize("epi", [0, 1, 3, 4])
+def test_gemm_mx_persistent_short_k_bit_identical(gpu, monkeypatch, short_cases, N, K, epi):
+    """The persistent stream (product library) against one workgroup per tile (A/B library,
+    MICLIP_MX_PERSIST=0) at short K, byte for byte: the same MFMAs in the same k order and the same
+    epilogue arithmetic, with the next tile's first stages issued from stage 1 / 3 / 7 of this one."""
+    import torch
+    N_ = _lib()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if ((SHORT_M + 255) // 256) * (N // 256) < cus:
+        pytest.skip(f"fewer tiles than the device's {cus} CUs: the persistent kernel is not dispatched")
+    ops = short_cases(gpu, N, K)
+    got = _short_run(N_.lib(), ops, N, K, epi)
+    monkeypatch.setenv("MICLIP_MX_PERSIST", "0")
+    ref = _short_run(N_.lib_ab(), ops, N, K, epi)
+    torch.cuda.synchronize()
+    assert torch.equal(got.view(torch.uint8), ref.view(torch.uint8))
+
+
+@pytest.mark.parametrize("N", SHORT_NS)
+@pytest.mark.parametrize("K", SHORT_KS)
+def test_gemm_mx_persistent_short_k_matches_oracle(gpu, short_cases, N, K):
+    """The same shapes' f32 output against oracle/mx_ref.gemm in float64 on 300 rows: the first and
+    middle rows and the partial tile's 116 (test_gemm_mx_matches_oracle's tolerance)."""
+    import torch
+    N_ = _lib()
+    M = SHORT_M
+    qa, sa, qw, sw, bias = ops = short_cases(gpu, N, K)
+    out = _short_run(N_.lib(), ops, N, K, 3)
+    torch.cuda.synchronize()
+    rows = np.r_[0:92, M // 2:M // 2 + 92, 16384:M]
+    assert len(rows) == 300
+    got = out[torch.from_numpy(rows).to(gpu)].double().cpu().numpy()
+    sa_ = mx_ref.from_stage_major(sa.cpu().numpy(), M, K)[rows]
+    sw_ = mx_ref.from_stage_major(sw.cpu().numpy(), N, K)
+    ref = mx_ref.gemm(qa.cpu().numpy()[rows], sa_, qw.cpu().numpy(), sw_) + bias.double().cpu().numpy()
+    tol = 1e-4 * np.abs(ref).max()
+    assert np.abs(got - ref).max() < tol, (np.abs(got - ref).max(), tol)
+
+
+def test_gemm_mx_cls_rows_fp8_output(gpu):
+    """The configs[4] CLS-row last block's c_fc (863 rows: 64 tiles, fewer than CUs, so one workgroup
+    per tile -- gemm_mxpp_kernel<EPI_GELU_MX>): decoded and checked as
+    test_gemm_mx_default_fp8_output_rows."""
+    test_gemm_mx_default_fp8_output_rows(gpu, 863, 4096, 1024)
