@@ -45,6 +45,24 @@ hipError_t with_value(int v, F&& f) {
   return r;
 }
 
+// The rank files' forms of both: f(std::integral_constant<int, DT>) for the corpus dtype (0 f32,
+// 1 bf16, 2 fp16) ...
+template <class F>
+static inline auto dispatch_dt(int dt, F&& f) {
+  return dt == 0   ? f(std::integral_constant<int, 0>{})
+         : dt == 1 ? f(std::integral_constant<int, 1>{})
+                   : f(std::integral_constant<int, 2>{});
+}
+// ... and a kernel chosen at run time with `lds` bytes of dynamic LDS (possibly above the 64 KB
+// default limit)
+template <class K, class... A>
+static inline hipError_t launch_lds(K fn, dim3 grid, int nt, size_t lds, hipStream_t s, A... args) {
+  const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fn, grid, dim3(nt), lds, s, args...);
+  return hipGetLastError();
+}
+
 // An A/B build's integer switch MICLIP_* from the environment (unset: fallback), read on every
 // call so that a test can switch it within one process; the product build has no switches and
 // takes the fallback at compile time.
@@ -56,6 +74,25 @@ inline int ab_env_int(const char* name, int fallback) {
 #else
 constexpr int ab_env_int(const char*, int fallback) { return fallback; }
 #endif
+
+// The A/B build's rank switches (MICLIP_RANK_*; rank.hip, rank_cert.hip, rank_mirror.hip), read on
+// every call; the product build holds the defaults at compile time.  Values are whole numbers
+// (atoi): an empty or non-numeric value reads as 0, and "10" is not "1".
+struct RankSwitches {
+  int nb;         // NB = 9: rank_reg with a 9-slot ring, 7 chunks in flight (8 / 6)
+  bool reg;       // REG = 0: rank_stream for D = 512 too
+  bool fold;      // FOLD = 1: the in-launch merge instead of the split merge
+  int cert;       // CERT: 0 never the certified pass, 2 for every eligible call whatever N
+  int cert_abl;   // CERT_ABL: rank_cert_kernel's timing probes
+  bool probe;     // PROBE = 1: rank_reg without its MFMAs (timing, wrong scores)
+  bool stamp;     // STAMP = 1: rank_reg's phase stamps (mi_debug_rank_stamp)
+};
+inline RankSwitches rank_switches() {
+  return {ab_env_int("MICLIP_RANK_NB", 8) == 9 ? 9 : 8, ab_env_int("MICLIP_RANK_REG", 1) != 0,
+          ab_env_int("MICLIP_RANK_FOLD", 0) == 1,       ab_env_int("MICLIP_RANK_CERT", 1),
+          ab_env_int("MICLIP_RANK_CERT_ABL", 0),        ab_env_int("MICLIP_RANK_PROBE", 0) == 1,
+          ab_env_int("MICLIP_RANK_STAMP", 0) == 1};
+}
 
 // A dispatch counts its work-items in 32 bits (grid x block < 2^32), so a kernel with `per_frame`
 // work-items per frame runs over chunks of frames: the frames per launch such that a launch has at

@@ -21,11 +21,11 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdlib>
 
 #include "common.hpp"
 #include "internal.hpp"
 #include "rank_pass.hpp"
+#include "rank_ring.hpp"
 
 namespace miclip {
 namespace {
@@ -111,28 +111,17 @@ __global__ __launch_bounds__(64 * NW) void rank_stream(const void* __restrict__ 
 //    v_mfma_f32_32x32x2_f32 chain, the fmaf sum of squares, inv_norm, keys,
 //    bitonic list update, tau threshold, workgroup list merge), so the
 //    candidates are bit-identical.
+// NB ring slots with NB - 2 chunks in flight (rank_ring.hpp; 8 / 6, A/B 9 / 7); the LDS is
+// rank_ring.hpp's layout with norms, for the launcher too.
 // NOMFMA: timing probe (the stream and the fragment reads without the MFMAs; wrong scores)
-// ILV (A/B, slower: see launch_reg): interleaved tile order.  Tile t of wave w
-// in workgroup g is global 32-row tile (t * NW + w) * G + g, so the whole grid
-// streams one contiguous band of NW * G tiles instead of G row ranges
-// rows_per_wg apart.  Candidates then carry global rows.
-// PIPE: a chunk's fragments are read from the ring one chunk ahead (two
-// register buffers), so the LDS latency hides under the previous chunk's MFMAs
-// instead of sitting between the wait and the MFMAs; the DMA lookahead is then
-// PF - 1 chunks beyond the one being read.
-// Dynamic LDS of rank_reg<.., NB, ..>: the ring [NW = 4][NB][4 KB], the per-wave
-// row norms [4][32] f32, tau [RQ] u32 and the lead keys [RQ][8].  The launcher sizes the allocation
-// with this same function: a kernel whose ring is larger than the allocation
-// puts its norms (and the last wave's slots) past the end of the workgroup's
-// LDS, where reads return zero — every score comes out 0.
-constexpr size_t rank_reg_lds_bytes(int NB) { return (size_t)4 * NB * (32 * 128) + 4 * 32 * 4 + RQ * 4 + LEAD_LDS; }
+template <int NB>
+using RegLds = RingLds<NB, true>;
 
 // STAMP (A/B build, MICLIP_RANK_STAMP=1): s_memrealtime (100 MHz) per workgroup at entry, after the query
 // load, after the stream, after fold_publish and at exit (mi_debug_rank_stamp)
 __device__ unsigned long long g_rank_stamp[256 * 10];
 
-template <int D, int NB = 8, int PF = 6, bool NOMFMA = false, bool ILV = false, bool PIPE = false, int DT = 0,
-          bool STAMP = false, bool SPLITM = true>
+template <int D, int NB, int DT, bool NOMFMA = false, bool STAMP = false, bool SPLITM = true>
 __global__ __launch_bounds__(256) void rank_reg(const void* __restrict__ corpus, int64_t N,
                                                 const float* __restrict__ queries, int64_t Q, int k,
                                                 int64_t rows_per_wg, int norm_mode, int nan_first, int64_t index_base,
@@ -144,28 +133,14 @@ __global__ __launch_bounds__(256) void rank_reg(const void* __restrict__ corpus,
   // DT 0: f32 rows, a ring chunk = 32 k; DT 1 / 2 (bf16 / fp16 rows): a ring chunk = 64 k, two
   // 32-k MFMA groups, converted to f32 (exactly) after the fragment read — the arithmetic of
   // rank_stream<DT> (load_chunk's conversion, the same k order), so its candidates bit for bit.
-  constexpr int ES = DT ? 2 : 4, NG = DT ? 2 : 1, NCH = D / (32 * NG), NQ = D / 32;
-  constexpr int NW = 4, NT = 64 * NW, KC = 16;
-  // NB ring slots per wave, PF chunks in flight (NB >= PF + 1: a refilled slot was read, and its
-  // reads waited for, in an earlier chunk iteration)
-  constexpr int SLOT = 32 * 128;           // 4 KB
-  // the invariants the ring's correctness rests on:
-  //  * a slot is refilled (chunk c + PF into slot (c + PF) % NB, issued at the top of chunk c's
-  //    iteration) only after the chunk it held, c + PF - NB, was read and its reads waited for
-  //    (lgkmcnt(0) in that chunk's iteration): c + PF - NB <= c - 1;
-  //  * the counted wait vmcnt(4 PF) (4 DMA instructions per chunk) fits the 6-bit vmcnt field;
-  //  * the ring, norms and tau fit the CU's 160 KB of LDS (and the launcher allocates exactly
-  //    rank_reg_lds_bytes(NB), which the list merge's 32 KB also fits in).
-  static_assert(NB >= PF + 1, "rank_reg: a refilled ring slot must have been read in an earlier chunk");
-  static_assert(4 * PF <= 63, "rank_reg: vmcnt(4 PF) exceeds the counter");
-  static_assert(rank_reg_lds_bytes(NB) <= 160 * 1024, "rank_reg: ring exceeds the LDS");
-  static_assert(rank_reg_lds_bytes(NB) >= (size_t)NT * KC * 8, "rank_reg: list merge area exceeds the allocation");
-  static_assert(rank_reg_lds_bytes(NB) >= fold_lds(NT), "rank_reg: in-launch merge area exceeds the allocation");
+  constexpr int NG = DT ? 2 : 1, NQ = D / 32;
+  constexpr int NW = RING_NW, KC = 16;
+  using Ring = RowRing<NB, NB - 2, D / (32 * NG)>;
+  using Lds = RegLds<NB>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ring = smem;                       // [NW][NB][SLOT]
-  float* nrm_all = (float*)(smem + NW * NB * SLOT);
-  uint32_t* tau = (uint32_t*)(nrm_all + NW * 32);
-  uint32_t* lead = tau + RQ;
+  float* nrm_all = (float*)(smem + Lds::nrm);
+  uint32_t* tau = (uint32_t*)(smem + Lds::tau);
+  uint32_t* lead = (uint32_t*)(smem + Lds::lead);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
@@ -196,99 +171,43 @@ __global__ __launch_bounds__(256) void rank_reg(const void* __restrict__ corpus,
   __syncthreads();
   if (STAMP && tid == 0) stamp[1] = __builtin_amdgcn_s_memrealtime();
 
-  const int G = NRB;
-  const int64_t r_begin = ILV ? 0 : (int64_t)RB * rows_per_wg;
-  const int64_t r_end = ILV ? N : min(N, r_begin + rows_per_wg);
+  // tile t of this wave: 32-row tile wave + t * NW of rows [r_begin, r_end)
+  const int64_t r_begin = (int64_t)RB * rows_per_wg;
+  const int64_t r_end = min(N, r_begin + rows_per_wg);
   const int nrows = (int)(r_end - r_begin);
   const int ntw = (nrows + 31) / 32;
-  // ILV: tiles (t * NW + wave) * G + blockIdx.x < ntw
-  const int sid = ILV ? wave * G + (int)RB : wave;
-  const int sstep = ILV ? NW * G : NW;
-  const int my_tiles = ntw > sid ? (ntw - 1 - sid) / sstep + 1 : 0;
+  const int my_tiles = ntw > wave ? (ntw - 1 - wave) / NW + 1 : 0;
   float* nrm = nrm_all + wave * 32;
-  char* wring = ring + wave * NB * SLOT;
-
-  // DMA: 4 x 1 KB per chunk; instruction m covers image rows 8m .. 8m + 7,
-  // lane l row 8m + (l >> 3), LDS slot (l & 7), source piece (l & 7) ^ ((row >> 1) & 7)
-  uint32_t voff[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int row = 8 * m + (lane >> 3);
-    const int c = (lane & 7) ^ ((row >> 1) & 7);
-    voff[m] = (uint32_t)(row * D * ES + c * 16);
-  }
-  int lt = 0, lj = 0, lslot = 0;           // load cursor: tile ordinal, chunk, ring slot
-  __amdgpu_buffer_rsrc_t rs;
-  auto make_rs = [&]() {
-    const int trow = (sid + sstep * lt) * 32;   // relative to r_begin
-    const int rows = max(0, min(32, nrows - trow));
-    // wave-uniform by construction; readfirstlane makes it provable (no waterfall loop per load, guide T20)
-    const uint64_t base = (uint64_t)(uintptr_t)((const char*)corpus + (r_begin + (rows ? trow : 0)) * (int64_t)D * ES);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-    const int nrec = __builtin_amdgcn_readfirstlane(rows * D * ES);
-    rs = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)hi << 32) | lo), (short)0, nrec, 0x00020000);
-  };
-  make_rs();
-  auto issue = [&]() {   // chunk (lt, lj) -> slot lslot; past this wave's tiles: range 0, zeros
-    char* dst = wring + lslot * SLOT;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (LDS_AS void*)(dst + m * 1024), 16, voff[m], lj * 128, 0, 0);
-    lslot = lslot == NB - 1 ? 0 : lslot + 1;
-    if (++lj == NCH) {
-      lj = 0;
-      ++lt;
-      make_rs();
-    }
-  };
-  // fragment read: row r, f32: k 16h .. 16h + 15 = slots 4h .. 4h + 3; 16-bit: k 32g + 16h .. + 15 =
-  // slots 4g + 2h, 4g + 2h + 1 for g = 0, 1 (permuted)
-  const int rbase = r * 128;
-  const int sw = (r >> 1) & 7;
+  Ring ring(corpus, r_begin, nrows, smem, wave, lane);
   uint64_t L[KC];
 #pragma unroll
   for (int p = 0; p < KC; ++p) L[p] = 0ull;
   uint32_t kk = 0u;   // running k-th key of this query's lists (own threshold)
 
+  // fragment read: row r, f32: k 16h .. 16h + 15 = pieces 4h .. 4h + 3; 16-bit: k 32g + 16h .. + 15 =
+  // pieces 4g + 2h, 4g + 2h + 1 for g = 0, 1
   auto read_frag = [&](int slot, float4 (&v)[4]) {
-    const char* src = wring + slot * SLOT + rbase;
 #pragma unroll
     for (int i4 = 0; i4 < 4; ++i4) {
-      const int sl = DT ? (i4 >> 1) * 4 + 2 * h + (i4 & 1) : 4 * h + i4;
-      const uint32_t a = (uint32_t)(uintptr_t)(const LDS_AS char*)(src + ((sl ^ sw) << 4));
-      asm volatile("ds_read_b128 %0, %1" : "=v"(v[i4]) : "v"(a) : "memory");
+      const int piece = DT ? (i4 >> 1) * 4 + 2 * h + (i4 & 1) : 4 * h + i4;
+      asm volatile("ds_read_b128 %0, %1" : "=v"(v[i4]) : "v"(ring.frag(slot, piece)) : "memory");
     }
   };
   if (my_tiles > 0) {
 #pragma unroll
-    for (int p = 0; p < PF; ++p) issue();
+    for (int p = 0; p < Ring::PF; ++p) ring.issue();
     int cslot = 0;
-    float4 vb[2][4];
-    if (PIPE) {   // chunk 0's fragments
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (PF - 1)) : "memory");
-      read_frag(0, vb[0]);
-      cslot = 1;
-    }
     for (int ct = 0; ct < my_tiles; ++ct) {
       f32x16 acc = f32x16{};
       float ss = 0.f;
 #pragma unroll
-      for (int j = 0; j < NCH; ++j) {
-        issue();   // chunk PF ahead (the ring slot it fills was read NB - PF chunks ago)
-        float4 (&v)[4] = vb[PIPE ? (j & 1) : 0];
-        if (PIPE) {
-          // the next chunk landed (PF - 1 younger); this chunk's fragments (read one chunk ago) are in v
-          asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(4 * (PF - 1)) : "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          read_frag(cslot, vb[(j + 1) & 1]);   // (past the last tile: a zero-range chunk, never used)
-          __builtin_amdgcn_sched_barrier(0);
-        } else {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * PF) : "memory");   // this chunk landed
-          read_frag(cslot, v);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-        }
+      for (int j = 0; j < Ring::NCH; ++j) {
+        ring.issue();   // chunk PF ahead (the ring slot it fills was read NB - PF chunks ago)
+        float4 v[4];
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Ring::WAIT) : "memory");   // this chunk landed
+        read_frag(cslot, v);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
           float cur[16];
@@ -328,12 +247,9 @@ __global__ __launch_bounds__(256) void rank_reg(const void* __restrict__ corpus,
       if (h == 0) nrm[r] = inv_norm(ss, norm_mode);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_wave_barrier();
-      const int tr0 = (sid + sstep * ct) * 32;
-      const uint32_t tq_thr = tau[r];
-      const uint32_t own = kk;   // the query's two half-lists' k-th: a lower bound of its k-th
-      const uint32_t thr0 = own > tq_thr ? own : tq_thr;
-      const uint32_t lb = lead_min(lead, r);
-      const uint32_t thr = lb > thr0 ? lb : thr0;
+      const int tr0 = ring.tile_row(ct);
+      uint32_t tq_thr;
+      const uint32_t thr = tile_threshold(tau, lead, r, kk, tq_thr);
       uint64_t c[16];
       bool any = false;
       uint32_t okm = 0u;
@@ -354,22 +270,19 @@ __global__ __launch_bounds__(256) void rank_reg(const void* __restrict__ corpus,
       }
       if (__any(any)) {
         list_update16(L, c, okm);
-        lead_publish(lead, r, 2 * wave + h, (uint32_t)(L[1] >> 32));
-        uint32_t kth = (uint32_t)(L[0] >> 32);
-#pragma unroll
-        for (int p = 1; p < KC; ++p) kth = (p == k - 1) ? (uint32_t)(L[p] >> 32) : kth;
-        const uint32_t other = (uint32_t)__shfl_xor((int)kth, 32, 64);
-        kth = kth > other ? kth : other;
-        kk = kth;
-        if (h == 0 && qvalid && kth > tq_thr) tau_max(&tau[r], kth);
+        kk = tile_publish(L, k, tau, lead, lane, wave, qvalid, tq_thr);
       }
       __builtin_amdgcn_wave_barrier();
     }
   }
-  // trailing (zero-range) DMAs and the pipelined read past the last chunk complete before the ring is reused
+  // trailing (zero-range) DMAs complete before the ring is reused
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   if (SPLITM) {   // split merge: the lists raw, then fold_merge_kernel (rank_keys.hpp)
-    lines_publish<NW>(L, smem, wave, lane, q0, Q, k, r_begin, f);
+    // the tail's lane id as a value of its own: hipcc otherwise shares r * 128 between the ring's
+    // fragment address and the tail's list address and keeps it (spilled, bf16 rows) across the stream
+    int tl = lane;
+    asm("" : "+v"(tl));
+    lines_publish<NW>(L, smem, wave, tl, q0, Q, k, r_begin, f);
     return;
   }
   fold_tail<NW>(L, smem, q0, Q, k, nan_first, r_begin, index_base, f, out_s, out_i, STAMP ? stamp : nullptr);
@@ -919,6 +832,15 @@ static FoldWs reg_fold(int64_t N, int64_t Q, void* ws) {
   return fold_ws(ws, (N + rpw - 1) / rpw, Q);
 }
 
+// one rank_reg instantiation with its own ring's LDS size
+template <int D, int DT, int NB, bool NOMFMA = false, bool STAMP = false, bool SPLITM = true>
+static hipError_t launch_reg_as(dim3 grid, hipStream_t s, const void* corpus, int64_t N, const float* q, int64_t Q, int k,
+                                int64_t rpw, int nm, int nf, int64_t base, FoldWs f, float* out_s, int64_t* out_i,
+                                const int32_t* gate) {
+  return launch_lds(rank_reg<D, NB, DT, NOMFMA, STAMP, SPLITM>, grid, 256, RegLds<NB>::bytes, s, corpus, N, q, Q, k, rpw,
+                    nm, nf, base, f, out_s, out_i, gate);
+}
+
 // prezeroed: the merge counters were cleared by the kernel before (the certified route's re-score)
 template <int D, int DT>
 static hipError_t launch_reg(int64_t N, const void* corpus, const float* q, int64_t Q, int k, int nm, int nf,
@@ -927,59 +849,34 @@ static hipError_t launch_reg(int64_t N, const void* corpus, const float* q, int6
   const int64_t rpw = reg_rows_per_wg(N);
   const int64_t nwg = (N + rpw - 1) / rpw;
   const FoldWs f = fold_ws(ws, nwg, Q);
-  // interleaved tile order: A/B only (MICLIP_RANK_ILV=1).  scripts/rank_micro.py: 1M x 512 494 us
-  // against 479 with contiguous row ranges, 1M x 768 729 against 717: not the stream's limit
-#if MICLIP_AB
-  const char* ilv = getenv("MICLIP_RANK_ILV");
-  const bool il = ilv && ilv[0] == '1';
-  // ring slots: MICLIP_RANK_NB=9 selects a 9-slot ring with 7 chunks in flight (A/B; round 2's
-  // 9-slot attempt kept this allocation at 8 slots' size, so its norms sat past the end of the
-  // LDS and read as zeros: every test failed, N = 1 included).  The size now follows NB.
-  const char* nbs = getenv("MICLIP_RANK_NB");
-  const bool nb9 = nbs && atoi(nbs) == 9;
-  const size_t lds = rank_reg_lds_bytes(nb9 ? 9 : 8);
-  const char* probe = getenv("MICLIP_RANK_PROBE");
-  // (7 chunks in flight measured the same: the stream alone, NOMFMA, reads 5.3 TB/s either way)
-  // fragment reads one chunk ahead: A/B only (MICLIP_RANK_PIPE=1; 1M x 512 552 us against 558,
-  // within noise: the wait before the MFMAs is not where this kernel loses time)
-  const char* pipe = getenv("MICLIP_RANK_PIPE");
-  const bool pp = pipe && pipe[0] == '1';
-  const char* stp = getenv("MICLIP_RANK_STAMP");
-  // in-launch merge (the round-4 tail) instead of the split merge: A/B (MICLIP_RANK_FOLD=1)
-  const char* fold = getenv("MICLIP_RANK_FOLD");
-  const bool inl = fold && fold[0] == '1';
-  auto fn = (stp && stp[0] == '1') ? rank_reg<D, 8, 6, false, false, false, DT, true, false>
-            : inl ? rank_reg<D, 8, 6, false, false, false, DT, false, false>
-            : nb9 ? rank_reg<D, 9, 7, false, false, false, DT>
-            : (probe && probe[0] == '1') ? (il ? rank_reg<D, 8, 6, true, true, false, DT> : rank_reg<D, 8, 6, true, false, false, DT>)
-            : il ? (pp ? rank_reg<D, 8, 6, false, true, true, DT> : rank_reg<D, 8, 6, false, true, false, DT>)
-                 : (pp ? rank_reg<D, 8, 6, false, false, true, DT> : rank_reg<D, 8, 6, false, false, false, DT>);
-#else   // product: the measured default (8 slots, 6 chunks in flight, contiguous row ranges)
-  const size_t lds = rank_reg_lds_bytes(8);
-  auto fn = rank_reg<D, 8, 6, false, false, false, DT>;
-  constexpr bool inl = false;
-#endif
+  // the measured default: 8 slots, 6 chunks in flight, contiguous row ranges, the split merge
+  auto launch = launch_reg_as<D, DT, 8>;
+  bool merged = false;   // the kernel merged in the launch
+  if constexpr (MICLIP_AB) {
+    const RankSwitches sw = rank_switches();
+    if (sw.stamp) launch = launch_reg_as<D, DT, 8, false, true, false>, merged = true;
+    else if (sw.fold) launch = launch_reg_as<D, DT, 8, false, false, false>, merged = true;
+    else if (sw.nb == 9) launch = launch_reg_as<D, DT, 9>;
+    else if (sw.probe) launch = launch_reg_as<D, DT, 8, true>;
+  }
   hipError_t e = hipSuccess;
   if (!prezeroed && (e = fold_zero(f, s)) != hipSuccess) return e;
   const dim3 grid((unsigned)((Q + RQ - 1) / RQ), (unsigned)nwg);   // (query blocks, row blocks): RB / QB
-  if ((e = launch_lds(fn, grid, 256, lds, s, corpus, N, q, Q, k, rpw, nm, nf, base, f, out_s, out_i, gate)) != hipSuccess)
-    return e;
-#if MICLIP_AB
-  if (inl || (stp && stp[0] == '1')) return hipSuccess;
-#endif
-  return inl ? hipSuccess : fold_merge(f, nwg, Q, k, nf, base, out_s, out_i, gate, s);
+  if ((e = launch(grid, s, corpus, N, q, Q, k, rpw, nm, nf, base, f, out_s, out_i, gate)) != hipSuccess || merged) return e;
+  return fold_merge(f, nwg, Q, k, nf, base, out_s, out_i, gate, s);
 }
 
-template <int DT, int NW>
+// 12 waves per workgroup, one workgroup per CU (~150 VGPRs, LDS = the list area)
+template <int DT>
 static hipError_t launch_stream(dim3 grid, hipStream_t s, const void* corpus, int64_t N, int64_t D, const float* q,
                                 int64_t Q, int k, int64_t rpw, int nm, int nf, int64_t base, void* ws, float* out_s,
                                 int64_t* out_i) {
+  constexpr int NW = 12;
   bool inl = false;   // the in-launch merge (A/B: MICLIP_RANK_FOLD=1)
-#if MICLIP_AB
-  const char* fold = getenv("MICLIP_RANK_FOLD");
-  inl = fold && fold[0] == '1';
-#endif
-  auto fn = inl ? rank_stream<DT, NW, false> : rank_stream<DT, NW, true>;
+  auto fn = rank_stream<DT, NW, true>;
+  if constexpr (MICLIP_AB) {
+    if ((inl = rank_switches().fold)) fn = rank_stream<DT, NW, false>;
+  }
   // tail: the (key, idx) lists [64 NW lanes][16] or the in-launch reducer's area
   const size_t lists = (size_t)64 * NW * 16 * 8;
   const size_t l = stream_lds(D, NW, lists > fold_lds(64 * NW) ? lists : fold_lds(64 * NW));
@@ -1003,20 +900,10 @@ hipError_t rank_topk(const void* corpus, int64_t N, int64_t D, int dt, const flo
   int64_t* ws_i = (int64_t*)((char*)ws + (size_t)(Q * nch * k) * sizeof(float));
   const dim3 grid((unsigned)((Q + RQ - 1) / RQ), (unsigned)nwg);   // (query blocks, row blocks): RB / QB
   const int KC = kc_for(k);
-  // streaming kernel for k <= 16 (KC = 16 lists stay in registers); 8 or 12
-  // waves per workgroup (MICLIP_RANK_NW A/B), one workgroup per CU either way
-  // (~150 VGPRs, LDS = the list area).  KC = 64 keeps rank_stage1 (its 64-deep
-  // lists would go to scratch in the streaming kernel).
-#if MICLIP_AB
-  const char* nwenv = getenv("MICLIP_RANK_NW");
-  const int NW = nwenv && atoi(nwenv) == 8 ? 8 : 12;
-  const char* legacy = getenv("MICLIP_RANK_STAGE1");   // A/B: the previous one-tile-at-a-time kernel
-  const char* noreg = getenv("MICLIP_RANK_REG");        // A/B: 0 = rank_stream for f32 D = 512 too
-#else
-  const char* legacy = nullptr;
-  const char* noreg = nullptr;
-#endif
-  if (KC == 16 && D == 512 && !(legacy && legacy[0] == '1') && !(noreg && noreg[0] == '0')) {
+  // streaming kernels for k <= 16 (KC = 16 lists stay in registers): rank_reg at D = 512
+  // (MICLIP_RANK_REG=0, A/B: rank_stream there too), rank_stream otherwise.  KC = 64 keeps
+  // rank_stage1 (its 64-deep lists would go to scratch in the streaming kernel).
+  if (KC == 16 && D == 512 && rank_switches().reg) {
     if (rank_cert_eligible(N, D, dt, k, norm_mode)) {
       // certified bf16-MFMA pass + exact re-score of its candidates, then the exact pass for
       // the query blocks it could not certify (results identical to the exact pass alone)
@@ -1035,24 +922,17 @@ hipError_t rank_topk(const void* corpus, int64_t N, int64_t D, int dt, const flo
       return launch_reg<512, DT()>(N, corpus, q, Q, k, norm_mode, nan_first, base, ws, out_s, out_i, s);
     });
   }
-  if (KC == 64 || (legacy && legacy[0] == '1')) {
+  if (KC == 64) {
     const hipError_t e = dispatch_dt(dt, [&](auto DT) {
-      auto stage1 = [&](auto fn, int kc) {
-        return launch_lds(fn, grid, 256, stage1_lds(D, kc), s, corpus, N, D, q, Q, k, rpw, norm_mode, nan_first, base,
-                          ws_s, ws_i, C);
-      };
-      return KC == 16 ? stage1(rank_stage1<16, DT()>, 16) : stage1(rank_stage1<64, DT()>, 64);
+      return launch_lds(rank_stage1<64, DT()>, grid, 256, stage1_lds(D, 64), s, corpus, N, D, q, Q, k, rpw, norm_mode,
+                        nan_first, base, ws_s, ws_i, C);
     });
     if (e != hipSuccess) return e;
     return rank_merge(ws_s, ws_i, Q, C, k, nan_first, out_s, out_i, s);
   }
   // k <= 16: rank_stream with the split (or, A/B, in-launch) merge
   return dispatch_dt(dt, [&](auto DT) {
-#if MICLIP_AB
-    if (NW == 8)
-      return launch_stream<DT(), 8>(grid, s, corpus, N, D, q, Q, k, rpw, norm_mode, nan_first, base, ws, out_s, out_i);
-#endif
-    return launch_stream<DT(), 12>(grid, s, corpus, N, D, q, Q, k, rpw, norm_mode, nan_first, base, ws, out_s, out_i);
+    return launch_stream<DT()>(grid, s, corpus, N, D, q, Q, k, rpw, norm_mode, nan_first, base, ws, out_s, out_i);
   });
 }
 

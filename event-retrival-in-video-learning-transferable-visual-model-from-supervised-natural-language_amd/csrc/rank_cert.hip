@@ -41,13 +41,12 @@
 
 #include <climits>
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
 #include "common.hpp"
 #include "internal.hpp"
-#include "rank_keys.hpp"
+#include "rank_ring.hpp"
 
 namespace miclip {
 namespace {
@@ -78,11 +77,9 @@ __device__ __forceinline__ void read_frag(const uint32_t (&fa)[4], f32x4c (&v)[4
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
-// the ring, per-wave row reciprocals [4][32], tau [32], the lead keys [32][8], the
-// per-wave candidate buckets [4][CBK][64] u64
+// the ring kernels' layout with norms; extra: the per-wave candidate buckets [4][CBK][64] u64
 constexpr int CNB = 8, CBK = 12;
-constexpr size_t cert_bucket_off() { return (size_t)4 * CNB * 4096 + 4 * 32 * 4 + 32 * 4 + LEAD_LDS; }
-constexpr size_t cert_lds_bytes() { return cert_bucket_off() + (size_t)4 * CBK * 64 * 8; }
+using CertLds = RingLds<CNB, true, (size_t)4 * CBK * 64 * 8>;
 
 // per wave (row block y < 256, wave w): tile-epilogue cycles, tiles, tiles with candidates, bucket flushes,
 // updates, multi-candidate insertion updates (ABL 5, A/B build; mi_debug_cert_probe)
@@ -97,28 +94,24 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
                                                         int64_t rows_per_wg, int norm_mode, int nan_first, FoldWs f,
                                                         int32_t* __restrict__ unsafe, float* __restrict__ out_s,
                                                         int64_t* __restrict__ out_i) {
-  constexpr int D = CD, NW = 4, NT = 64 * NW, KC = CKC, NB = CNB;
-  // chunks in flight: bf16 rows read their fragments one chunk ahead, so a slot is free once
-  // its fragments have arrived (PF = NB); f32 rows read the chunk itself (PF = NB - 1)
-  constexpr int PF = DT ? NB : NB - 1;
+  constexpr int D = CD, NW = RING_NW, KC = CKC, NB = CNB;
   constexpr int ES = DT ? 2 : 4;           // bytes per element
   constexpr int KCH = 128 / ES;            // k per 4-KB chunk (32 rows x 128 B)
   constexpr int NCH = D / KCH;             // chunks per 32-row tile
   constexpr int NS = D / 16;               // bf16 MFMA k-steps
-  constexpr int SLOT = 32 * 128;
-  static_assert(NB >= PF + (DT ? 0 : 1), "rank_cert: a refilled ring slot must have been read in an earlier chunk");
-  static_assert(4 * PF <= 63, "rank_cert: vmcnt(4 PF) exceeds the counter");
-  static_assert(cert_lds_bytes() <= 160 * 1024, "rank_cert: ring exceeds the LDS");
-  static_assert(cert_lds_bytes() >= (size_t)NT * KC * 8, "rank_cert: list merge area exceeds the allocation");
-  static_assert(cert_lds_bytes() >= fold_lds(NT), "rank_cert: in-launch merge area exceeds the allocation");
+  // bf16 rows read their fragments one chunk ahead (two register buffers, as the mirror pass), so a
+  // slot is free once its fragments have arrived (PF = NB); f32 rows read the chunk itself, after
+  // its wait (PF = NB - 1, one buffer: the split's temporaries need the VGPRs)
+  constexpr bool PIPE = DT != 0;
+  using Ring = RowRing<NB, PIPE ? NB : NB - 1, NCH, PIPE>;
+  constexpr int SLOT = Ring::SLOT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ring = smem;
-  float* nrm_all = (float*)(smem + NW * NB * SLOT);
-  uint32_t* tau = (uint32_t*)(nrm_all + NW * 32);
-  uint32_t* lead = tau + 32;
+  float* nrm_all = (float*)(smem + CertLds::nrm);
+  uint32_t* tau = (uint32_t*)(smem + CertLds::tau);
+  uint32_t* lead = (uint32_t*)(smem + CertLds::lead);
   const int tid = threadIdx.x, lane = tid & 63;
   // this lane's candidate bucket: slot j at bkt + 512 j (slot-major, conflict-free)
-  const uint32_t bkt = (uint32_t)(uintptr_t)(LDS_AS char*)(smem + cert_bucket_off()) +
+  const uint32_t bkt = (uint32_t)(uintptr_t)(LDS_AS char*)(smem + CertLds::extra) +
                        (uint32_t)((tid >> 6) * CBK * 512 + (tid & 63) * 8);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
@@ -154,44 +147,8 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
   const int64_t nrows = r_end - r_begin;
   const int ntw = (int)((nrows + 31) / 32);
   const int my_tiles = ntw > wave ? (ntw - 1 - wave) / NW + 1 : 0;
-  char* wring = ring + wave * NB * SLOT;
   float* nrm = nrm_all + wave * 32;
-
-  // DMA: 4 x 1 KB per chunk; instruction m covers image rows 8m .. 8m + 7,
-  // lane l row 8m + (l >> 3), LDS slot (l & 7), source piece (l & 7) ^ ((row >> 1) & 7)
-  uint32_t voff[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int row = 8 * m + (lane >> 3);
-    const int c = (lane & 7) ^ ((row >> 1) & 7);
-    voff[m] = (uint32_t)(row * D * ES + c * 16);
-  }
-  int lt = 0, lj = 0, lslot = 0;
-  __amdgpu_buffer_rsrc_t rs;
-  auto make_rs = [&]() {
-    const int64_t trow = (int64_t)(wave + NW * lt) * 32;   // relative to r_begin
-    const int rows = (int)max((int64_t)0, min((int64_t)32, nrows - trow));
-    const uint64_t base = (uint64_t)(uintptr_t)((const char*)corpus + (r_begin + (rows ? trow : 0)) * (int64_t)D * ES);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-    const int nrec = __builtin_amdgcn_readfirstlane(rows * D * ES);
-    rs = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)hi << 32) | lo), (short)0, nrec, 0x00020000);
-  };
-  make_rs();
-  auto issue = [&]() {
-    char* dst = wring + lslot * SLOT;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (LDS_AS void*)(dst + m * 1024), 16, voff[m], lj * 128, 0, 0);
-    lslot = lslot == NB - 1 ? 0 : lslot + 1;
-    if (++lj == NCH) {
-      lj = 0;
-      ++lt;
-      make_rs();
-    }
-  };
-  const int rbase = r * 128;
-  const int sw = (r >> 1) & 7;
+  Ring ring(corpus, r_begin, (int)nrows, smem, wave, lane);
   // fragment pieces of this lane in a chunk: bf16 rows, k-step t: piece 2t + h;
   // f32 rows, k-step t: pieces 4t + 2h and 4t + 2h + 1
   // The 16-row tile takes NCH chunks and NCH is a multiple of NB, so the slot a chunk
@@ -201,10 +158,7 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
   static_assert(NCH % NB == 0, "rank_cert: the ring slot of a chunk must be static");
   uint32_t fa[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int piece = DT ? 2 * t + h : 4 * (t >> 1) + 2 * h + (t & 1);
-    fa[t] = (uint32_t)(uintptr_t)(const LDS_AS char*)(wring + rbase + ((piece ^ sw) << 4));
-  }
+  for (int t = 0; t < 4; ++t) fa[t] = ring.frag(0, DT ? 2 * t + h : 4 * (t >> 1) + 2 * h + (t & 1));
   uint64_t L[KC];
 #pragma unroll
   for (int p = 0; p < KC; ++p) L[p] = 0ull;
@@ -245,13 +199,10 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
 
   if (my_tiles > 0) {
 #pragma unroll
-    for (int p = 0; p < PF; ++p) issue();
-    // bf16 rows: fragments read one chunk ahead (two register buffers, as the mirror pass);
-    // f32 rows: one buffer, read after the chunk's wait (the split's temporaries need the VGPRs)
-    constexpr bool PIPE = DT != 0;
+    for (int p = 0; p < Ring::PF; ++p) ring.issue();
     f32x4c vb[PIPE ? 2 : 1][4];
     if (PIPE) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (PF - 1)) : "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Ring::WAIT) : "memory");
       read_frag<0>(fa, vb[0]);
     }
     for (int ct = 0; ct < my_tiles; ++ct) {
@@ -265,15 +216,15 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
         // bf16: this chunk's fragments (read in the previous chunk) have arrived before its
         // slot is refilled with chunk j + PF (PF = NB)
         if (PIPE) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        issue();
+        ring.issue();
         f32x4c (&v)[4] = vb[PIPE ? (j & 1) : 0];
         if (PIPE) {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (PF - 1)) : "memory");
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Ring::WAIT) : "memory");
           __builtin_amdgcn_sched_barrier(0);
           read_frag<(j + 1) % NB * SLOT>(fa, vb[PIPE ? ((j + 1) & 1) : 0]);
           __builtin_amdgcn_sched_barrier(0);
         } else {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * PF) : "memory");
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Ring::WAIT) : "memory");
           read_frag<j % NB * SLOT>(fa, v);
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_sched_barrier(0);
@@ -341,7 +292,7 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
       } else {
         ss += __shfl_xor(ss, 32, 64);
       }
-      const int tr0 = (wave + NW * ct) * 32;
+      const int tr0 = ring.tile_row(ct);
       const bool rvalid = (int64_t)tr0 + r < nrows;
       // also the scores' guard: with the sum of squares in range and a finite query of
       // moderate norm (checked at entry) every score is finite
@@ -355,11 +306,8 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_wave_barrier();
       if (ABL == 5) pr_t0 = __builtin_amdgcn_s_memtime();
-      const uint32_t tq_thr = tau[r];
-      const uint32_t own = kk;   // the query's two half-lists' k-th: a lower bound of its k-th
-      const uint32_t thr0 = own > tq_thr ? own : tq_thr;
-      const uint32_t lb = lead_min(lead, r);
-      const uint32_t thr = lb > thr0 ? lb : thr0;
+      uint32_t tq_thr;
+      const uint32_t thr = tile_threshold(tau, lead, r, kk, tq_thr);
       // the key threshold as a score: score_key is monotone on finite scores (-0 = +0), so
       // key >= thr <=> s >= tf; keys below key(-inf) admit every finite score
       const float tf = thr < 0x00800000u ? -INFINITY
@@ -405,17 +353,10 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
           }
           okm = 0u;
         }
-        {
-          // lane id recomputed (v_mbcnt): a live-across-the-tile LDS address gets spilled, and
-          // its reload's vmcnt(0) would drain the ring
-          const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-          lead_publish(lead, ln & 31, 2 * wave + (ln >> 5), (uint32_t)(L[1] >> 32));
-        }
-        uint32_t kth = (uint32_t)(L[KC - 1] >> 32);   // k = kc = KC candidates
-        const uint32_t other = (uint32_t)__shfl_xor((int)kth, 32, 64);
-        kth = kth > other ? kth : other;
-        kk = kth;
-        if (h == 0 && qvalid && kth > tq_thr) tau_max(&tau[r], kth);
+        // lane id recomputed (v_mbcnt): a live-across-the-tile LDS address gets spilled, and
+        // its reload's vmcnt(0) would drain the ring
+        const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        kk = tile_publish(L, KC, tau, lead, ln, wave, qvalid, tq_thr);   // k = kc = KC candidates
       }
       pokm = okm;
       if (ABL == 5) {
@@ -450,12 +391,10 @@ __global__ __launch_bounds__(256) void rank_cert_kernel(const void* __restrict__
 }  // namespace
 
 int64_t rank_cert_min_rows() {
-#if MICLIP_AB
   // MICLIP_RANK_CERT (A/B): 0 = never, 2 = every eligible call regardless of N (tests)
-  const char* e = getenv("MICLIP_RANK_CERT");
-  if (e && e[0] == '0') return INT64_MAX;
-  if (e && e[0] == '2') return 1;
-#endif
+  const int sw = rank_switches().cert;
+  if (sw == 0) return INT64_MAX;
+  if (sw == 2) return 1;
   // below ~256k rows the fixed re-score and merge cost eat the gain (the mirror's threshold)
   return 262144;
 }
@@ -502,29 +441,22 @@ hipError_t rank_cert_topk(const void* corpus, int64_t N, int dt, const float* q,
   // each fill is a ~5 us dispatch of its own at this size (scripts/gpu_r4p.sh trace)
   int32_t* unsafe = (int32_t*)fu.aux;
   if ((e = fold_zero(fu, s)) != hipSuccess) return e;
-  const size_t lds = cert_lds_bytes();
   const dim3 grid((unsigned)((Q + FQ - 1) / FQ), (unsigned)nwg_used);   // (query blocks, row blocks)
-#if MICLIP_AB
-  const char* ab = getenv("MICLIP_RANK_CERT_ABL");   // timing probes (wrong results)
-  const int abl = ab ? atoi(ab) : 0;
-#endif
   auto fn = dt == 0 ? rank_cert_kernel<0> : rank_cert_kernel<1>;
   bool inl = false;   // the in-launch merge (A/B: MICLIP_RANK_FOLD=1)
 #if MICLIP_AB
-  const char* fold = getenv("MICLIP_RANK_FOLD");
-  inl = fold && fold[0] == '1';
-  if (inl) fn = dt == 0 ? rank_cert_kernel<0, 0, false> : rank_cert_kernel<1, 0, false>;
-  if (abl == 1) fn = dt == 0 ? rank_cert_kernel<0, 1> : rank_cert_kernel<1, 1>;
-  else if (abl == 2) fn = dt == 0 ? rank_cert_kernel<0, 2> : rank_cert_kernel<1, 2>;
-  else if (abl == 3) fn = dt == 0 ? rank_cert_kernel<0, 3> : rank_cert_kernel<1, 3>;
-  else if (abl == 5) fn = dt == 0 ? rank_cert_kernel<0, 5> : rank_cert_kernel<1, 5>;
-  else if (abl == 6) fn = dt == 0 ? rank_cert_kernel<0, 6> : rank_cert_kernel<1, 6>;
-  else if (abl == 7) fn = dt == 0 ? rank_cert_kernel<0, 7> : rank_cert_kernel<1, 7>;
+  const RankSwitches sw = rank_switches();
+  if ((inl = sw.fold)) fn = dt == 0 ? rank_cert_kernel<0, 0, false> : rank_cert_kernel<1, 0, false>;
+  // MICLIP_RANK_CERT_ABL: the timing probes (wrong results); 0 and every value outside the list
+  // keep the kernel chosen above, so with_value's "not in the list" answer is no error here
+  (void)with_value<1, 2, 3, 5, 6, 7>(sw.cert_abl, [&](auto ABL) {
+    fn = dt == 0 ? rank_cert_kernel<0, ABL()> : rank_cert_kernel<1, ABL()>;
+    return hipSuccess;
+  });
 #endif
-  if ((e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
+  if ((e = launch_lds(fn, grid, 256, CertLds::bytes, s, corpus, N, q, Q, CKC, rpw, norm_mode, nan_first, fu, unsafe, m_s,
+                      m_i)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, corpus, N, q, Q, CKC, rpw, norm_mode, nan_first, fu, unsafe, m_s, m_i);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
   if (!inl && (e = fold_merge(fu, nwg_used, Q, CKC, nan_first, 0, m_s, m_i, nullptr, s)) != hipSuccess) return e;
   float d_rel, d_abs;
   rank_cert_delta(dt, d_rel, d_abs);

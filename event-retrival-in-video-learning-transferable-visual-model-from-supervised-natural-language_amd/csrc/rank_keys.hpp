@@ -142,6 +142,32 @@ __device__ __forceinline__ void lead_publish(uint32_t* lead, int r, int list, ui
   asm volatile("ds_write_b32 %0, %1" ::"v"(a), "v"(key) : "memory");
 }
 
+// The ring kernels' tile threshold (lane (r, h): query r): a candidate must reach the query's
+// running k-th key kk (its two half-lists'), the workgroup's tau[r] (returned in tq for
+// tile_publish) and the lead bound, each a lower bound of the query's k-th key.
+__device__ __forceinline__ uint32_t tile_threshold(const uint32_t* tau, const uint32_t* lead, int r, uint32_t kk,
+                                                   uint32_t& tq) {
+  tq = tau[r];
+  const uint32_t thr0 = kk > tq ? kk : tq;
+  const uint32_t lb = lead_min(lead, r);
+  return lb > thr0 ? lb : thr0;
+}
+// ... and their publish step after a list update: the list's second key to lead, the k-th key
+// (k = 16 at compile time: L[15]) maxed with the other half-wave's raises tau[r]; returns it, the
+// new kk.  lane: this lane's id (rank_cert_kernel passes a recomputed one).
+__device__ __forceinline__ uint32_t tile_publish(const uint64_t (&L)[16], int k, uint32_t* tau, uint32_t* lead,
+                                                 int lane, int wave, bool qvalid, uint32_t tq) {
+  const int r = lane & 31, h = lane >> 5;
+  lead_publish(lead, r, 2 * wave + h, (uint32_t)(L[1] >> 32));
+  uint32_t kth = (uint32_t)(L[0] >> 32);
+#pragma unroll
+  for (int p = 1; p < 16; ++p) kth = (p == k - 1) ? (uint32_t)(L[p] >> 32) : kth;
+  const uint32_t other = (uint32_t)__shfl_xor((int)kth, 32, 64);
+  kth = kth > other ? kth : other;
+  if (h == 0 && qvalid && kth > tq) tau_max(&tau[r], kth);
+  return kth;
+}
+
 // A tile's candidates c[0..15] (0 = none; m: the non-empty ones) into the
 // sorted (desc) top-16 list L.  Once the threshold has settled a lane has 0 or
 // 1 candidate per tile, and a full bitonic sort + merge (~1000 instructions of

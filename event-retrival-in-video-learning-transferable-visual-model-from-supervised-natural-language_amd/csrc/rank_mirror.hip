@@ -36,11 +36,10 @@
 
 #include <climits>
 #include <cmath>
-#include <cstdlib>
 
 #include "common.hpp"
 #include "internal.hpp"
-#include "rank_keys.hpp"
+#include "rank_ring.hpp"
 
 namespace miclip {
 namespace {
@@ -49,6 +48,8 @@ using namespace rankk;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 constexpr int MQ = 32;   // queries per workgroup (MFMA N)
+constexpr int MIRROR_NB = 8;
+using MirrorLds = RingLds<MIRROR_NB, false>;   // (unit rows: no norms)
 
 // ---- mirror build: 32 rows per wave (lane = (row, half) as the rank kernels load them)
 template <int DT>
@@ -85,21 +86,19 @@ __global__ __launch_bounds__(256) void mirror_build_kernel(const void* __restric
   }
 }
 
-// ---- mirror ranking pass (see the file comment)
-// ILV: interleaved tile order (rank.hip rank_reg); otherwise each workgroup
-// streams rows_per_wg contiguous rows
-// PIPE: fragments read one chunk ahead (rank.hip rank_reg)
-template <int D, bool SPLIT, bool ILV = false, bool PIPE = true, int NB = 8, int PF = 6, bool SPLITM = true>
+// ---- mirror ranking pass (see the file comment): each workgroup streams rows_per_wg contiguous
+// rows through an 8-slot ring with 6 chunks in flight, fragments read one chunk ahead
+template <int D, bool SPLIT, bool SPLITM = true>
 __global__ __launch_bounds__(256) void rank_mirror_kernel(const uint16_t* __restrict__ mirror, int64_t N,
                                                           const float* __restrict__ queries, int64_t Q, int k,
                                                           int64_t rows_per_wg, int nan_first, FoldWs f,
                                                           float* __restrict__ out_s, int64_t* __restrict__ out_i) {
-  constexpr int NW = 4, KC = 16, NCH = D / 64, NS = D / 16;
-  constexpr int SLOT = 32 * 128;   // 32 rows x 64 k fp16
+  constexpr int NW = RING_NW, KC = 16, NS = D / 16;
+  using Ring = RowRing<MIRROR_NB, 6, D / 64, true>;   // a chunk: 32 rows x 64 k fp16
+  using Lds = MirrorLds;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ring = smem;   // [NW][NB][SLOT]
-  uint32_t* tau = (uint32_t*)(smem + NW * NB * SLOT);
-  uint32_t* lead = tau + MQ;
+  uint32_t* tau = (uint32_t*)(smem + Lds::tau);
+  uint32_t* lead = (uint32_t*)(smem + Lds::lead);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
@@ -128,105 +127,51 @@ __global__ __launch_bounds__(256) void rank_mirror_kernel(const uint16_t* __rest
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // tile t of this wave: 32-row tile sid + t * sstep of rows [r_begin, r_end)
-  const int G = NRB;
-  const int64_t r_begin = ILV ? 0 : (int64_t)RB * rows_per_wg;
-  const int64_t r_end = ILV ? N : min(N, r_begin + rows_per_wg);
+  // tile t of this wave: 32-row tile wave + t * NW of rows [r_begin, r_end)
+  const int64_t r_begin = (int64_t)RB * rows_per_wg;
+  const int64_t r_end = min(N, r_begin + rows_per_wg);
   const int64_t nrows = r_end - r_begin;
   const int ntw = (int)((nrows + 31) / 32);
-  const int sid = ILV ? wave * G + (int)RB : wave, sstep = ILV ? NW * G : NW;
-  const int my_tiles = ntw > sid ? (ntw - 1 - sid) / sstep + 1 : 0;
-  char* wring = ring + wave * NB * SLOT;
-
-  // DMA: 4 x 1 KB per chunk; instruction m covers image rows 8m .. 8m + 7,
-  // lane l row 8m + (l >> 3), LDS slot (l & 7), source piece (l & 7) ^ ((row >> 1) & 7)
-  uint32_t voff[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int row = 8 * m + (lane >> 3);
-    const int c = (lane & 7) ^ ((row >> 1) & 7);
-    voff[m] = (uint32_t)(row * D * 2 + c * 16);
-  }
-  int lt = 0, lj = 0, lslot = 0;
-  __amdgpu_buffer_rsrc_t rs;
-  auto make_rs = [&]() {
-    const int64_t trow = (int64_t)(sid + sstep * lt) * 32;   // relative to r_begin
-    const int rows = (int)max((int64_t)0, min((int64_t)32, nrows - trow));
-    const uint64_t base = (uint64_t)(uintptr_t)(mirror + (r_begin + (rows ? trow : 0)) * (int64_t)D);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-    const int nrec = __builtin_amdgcn_readfirstlane(rows * D * 2);
-    rs = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)hi << 32) | lo), (short)0, nrec, 0x00020000);
-  };
-  make_rs();
-  auto issue = [&]() {
-    char* dst = wring + lslot * SLOT;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (LDS_AS void*)(dst + m * 1024), 16, voff[m], lj * 128, 0, 0);
-    lslot = lslot == NB - 1 ? 0 : lslot + 1;
-    if (++lj == NCH) {
-      lj = 0;
-      ++lt;
-      make_rs();
-    }
-  };
-  const int rbase = r * 128;
-  const int sw = (r >> 1) & 7;
+  const int my_tiles = ntw > wave ? (ntw - 1 - wave) / NW + 1 : 0;
+  Ring ring(mirror, r_begin, (int)nrows, smem, wave, lane);
   uint64_t L[KC];
 #pragma unroll
   for (int p = 0; p < KC; ++p) L[p] = 0ull;
   uint32_t kk = 0u;   // running k-th key of this query's lists (own threshold)
 
-  auto read_frag = [&](int slot, f32x4v (&v)[4]) {
-    const char* src = wring + slot * SLOT + rbase;
+  auto read_frag = [&](int slot, f32x4v (&v)[4]) {   // k-step t of the chunk: piece 2t + h
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const uint32_t a = (uint32_t)(uintptr_t)(const LDS_AS char*)(src + (((2 * t + h) ^ sw) << 4));
-      asm volatile("ds_read_b128 %0, %1" : "=v"(v[t]) : "v"(a) : "memory");
-    }
+    for (int t = 0; t < 4; ++t) asm volatile("ds_read_b128 %0, %1" : "=v"(v[t]) : "v"(ring.frag(slot, 2 * t + h)) : "memory");
   };
   if (my_tiles > 0) {
 #pragma unroll
-    for (int p = 0; p < PF; ++p) issue();
-    int cslot = 0;
+    for (int p = 0; p < Ring::PF; ++p) ring.issue();
     f32x4v vb[2][4];
-    if (PIPE) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (PF - 1)) : "memory");
-      read_frag(0, vb[0]);
-      cslot = 1;
-    }
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Ring::WAIT) : "memory");
+    read_frag(0, vb[0]);
+    int cslot = 1;
     for (int ct = 0; ct < my_tiles; ++ct) {
       f32x16 acc = f32x16{};
 #pragma unroll
-      for (int j = 0; j < NCH; ++j) {
-        issue();
-        f32x4v (&v)[4] = vb[PIPE ? (j & 1) : 0];
-        if (PIPE) {
-          asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(4 * (PF - 1)) : "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          read_frag(cslot, vb[(j + 1) & 1]);
-          __builtin_amdgcn_sched_barrier(0);
-        } else {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * PF) : "memory");
-          read_frag(cslot, v);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-        }
+      for (int j = 0; j < Ring::NCH; ++j) {
+        ring.issue();
+        f32x4v (&v)[4] = vb[j & 1];
+        // the next chunk landed; this chunk's fragments (read one chunk ago) are in v
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(Ring::WAIT) : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        read_frag(cslot, vb[(j + 1) & 1]);   // (past the last tile: a zero-range chunk, never used)
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const f16x8 av = __builtin_bit_cast(f16x8, v[t]);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, qh[4 * j + t], acc, 0, 0, 0);
           if (SPLIT) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, ql[4 * j + t], acc, 0, 0, 0);
         }
-        cslot = cslot == NB - 1 ? 0 : cslot + 1;
+        cslot = cslot == Ring::NB - 1 ? 0 : cslot + 1;
       }
-      const int tr0 = (sid + sstep * ct) * 32;
-      const uint32_t tq_thr = tau[r];
-      const uint32_t own = kk;   // the query's two half-lists' k-th: a lower bound of its k-th
-      const uint32_t thr0 = own > tq_thr ? own : tq_thr;
-      const uint32_t lb = lead_min(lead, r);
-      const uint32_t thr = lb > thr0 ? lb : thr0;
+      const int tr0 = ring.tile_row(ct);
+      uint32_t tq_thr;
+      const uint32_t thr = tile_threshold(tau, lead, r, kk, tq_thr);
       uint64_t c[16];
       bool any = false;
       uint32_t okm = 0u;
@@ -242,12 +187,7 @@ __global__ __launch_bounds__(256) void rank_mirror_kernel(const uint16_t* __rest
       }
       if (__any(any)) {
         list_update16(L, c, okm);
-        lead_publish(lead, r, 2 * wave + h, (uint32_t)(L[1] >> 32));
-        uint32_t kth = (uint32_t)(L[KC - 1] >> 32);   // k = kc = KC candidates
-        const uint32_t other = (uint32_t)__shfl_xor((int)kth, 32, 64);
-        kth = kth > other ? kth : other;
-        kk = kth;
-        if (h == 0 && qvalid && kth > tq_thr) tau_max(&tau[r], kth);
+        kk = tile_publish(L, KC, tau, lead, lane, wave, qvalid, tq_thr);   // k = kc = KC candidates
       }
       __builtin_amdgcn_wave_barrier();
     }
@@ -402,31 +342,18 @@ namespace miclip {
 template <int D, bool SPLIT>
 static hipError_t launch_mirror(const uint16_t* mirror, int64_t N, const float* q, int64_t Q, int kc, int nf,
                                 void* fws, float* out_s, int64_t* out_i, int64_t nwg, hipStream_t s) {
-  const size_t lds = (size_t)4 * 8 * 4096 + MQ * 4 + LEAD_LDS;
   const int64_t rpw = ((N + nwg - 1) / nwg + 127) / 128 * 128;   // whole tiles per wave round
-  // MICLIP_MIRROR_VAR (A/B): 1 fragments read after the wait (no PIPE), 2 seven chunks in
-  // flight, 3 interleaved tiles
-#if MICLIP_AB
-  const char* var = getenv("MICLIP_MIRROR_VAR");
-  const int v = var ? atoi(var) : 0;
-  // MICLIP_RANK_FOLD=1 (A/B): the in-launch merge instead of the split merge
-  const char* fold = getenv("MICLIP_RANK_FOLD");
-  const bool inl = fold && fold[0] == '1';
-  auto fn = inl ? rank_mirror_kernel<D, SPLIT, false, true, 8, 6, false>
-            : v == 1 ? rank_mirror_kernel<D, SPLIT, false, false>
-            : v == 2 ? rank_mirror_kernel<D, SPLIT, false, true, 8, 7>
-            : v == 3 ? rank_mirror_kernel<D, SPLIT, true> : rank_mirror_kernel<D, SPLIT>;
-#else
+  bool inl = false;   // the in-launch merge instead of the split merge (A/B: MICLIP_RANK_FOLD=1)
   auto fn = rank_mirror_kernel<D, SPLIT>;
-  constexpr bool inl = false;
-#endif
-  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
+  if constexpr (MICLIP_AB) {
+    if ((inl = rank_switches().fold)) fn = rank_mirror_kernel<D, SPLIT, false>;
+  }
   const dim3 grid((unsigned)((Q + MQ - 1) / MQ), (unsigned)nwg);   // (query blocks, row blocks): RB / QB
   const FoldWs f = fold_ws(fws, nwg, Q);
-  if ((e = fold_zero(f, s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, mirror, N, q, Q, kc, rpw, nf, f, out_s, out_i);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipError_t e = fold_zero(f, s);
+  if (e != hipSuccess) return e;
+  if ((e = launch_lds(fn, grid, 256, MirrorLds::bytes, s, mirror, N, q, Q, kc, rpw, nf, f, out_s, out_i)) != hipSuccess)
+    return e;
   return inl ? hipSuccess : fold_merge(f, nwg, Q, kc, nf, 0, out_s, out_i, nullptr, s);
 }
 
@@ -455,22 +382,12 @@ hipError_t rank_rescore(const void* master, int64_t N, int64_t D, int dt, const 
                         hipStream_t s, uint32_t* zero, int64_t zero_words) {
   if (Q <= 0) return hipSuccess;
   const dim3 grid((unsigned)Q);
-#define MI_RS(DTV, DV)                                                                                                \
-  hipLaunchKernelGGL((mirror_rescore_kernel<DTV, DV>), grid, dim3(64), 0, s, master, N, q, k, kc, m_s, m_i, base, \
-                     d_rel, d_abs, norm_mode, nan_first, unsafe, out_s, out_i, cert, zero, zero_words)
-  if (D == 512) {
-    if (dt == 0) MI_RS(0, 512);
-    else if (dt == 1) MI_RS(1, 512);
-    else MI_RS(2, 512);
-  } else if (D == 768) {
-    if (dt == 0) MI_RS(0, 768);
-    else if (dt == 1) MI_RS(1, 768);
-    else MI_RS(2, 768);
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef MI_RS
-  return hipGetLastError();
+  return dispatch_dt(dt, [&](auto DT) {
+    return with_value<512, 768>(D <= 768 ? (int)D : 0, [&](auto DV) {
+      return launch_kernel(mirror_rescore_kernel<DT(), DV()>, grid, 64, s, master, N, q, k, kc, m_s, m_i, base, d_rel,
+                           d_abs, norm_mode, nan_first, unsafe, out_s, out_i, cert, zero, zero_words);
+    });
+  });
 }
 
 }  // namespace miclip

@@ -3,7 +3,7 @@
 // rank_filter_tiles: k <= 64), with the blocks they are made of (query staging, the 32-k chunk,
 // score_tile).  A visible row's score is the same instruction sequence under every policy, which
 // is what makes filtered and unfiltered results bit-identical.  Host side: the workgroup split of
-// the rows, the LDS sizes and the launch helpers the launchers of both files share.
+// the rows and the LDS sizes the launchers of both files share (dispatch_dt / launch_lds: internal.hpp).
 //
 // A row policy answers, for one wave of a workgroup whose tile t (ordinal) starts at row
 // (wave + NW t) * 32 of the workgroup's range:
@@ -279,23 +279,6 @@ static inline size_t stage1_lds(int64_t D, int KC) {
   const size_t qa = (size_t)FQ * (D + 4) * 4 + 4 * 32 * 4;
   const size_t la = (size_t)256 * KC * 8;
   return qa > la ? qa : la;
-}
-
-// f(std::integral_constant<int, DT>) for the corpus dtype (0 f32, 1 bf16, 2 fp16)
-template <class F>
-static inline auto dispatch_dt(int dt, F&& f) {
-  return dt == 0   ? f(std::integral_constant<int, 0>{})
-         : dt == 1 ? f(std::integral_constant<int, 1>{})
-                   : f(std::integral_constant<int, 2>{});
-}
-
-// a kernel with `lds` bytes of dynamic LDS (possibly above the 64 KB default limit)
-template <class K, class... A>
-static inline hipError_t launch_lds(K fn, dim3 grid, int nt, size_t lds, hipStream_t s, A... args) {
-  const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(fn, grid, dim3(nt), lds, s, args...);
-  return hipGetLastError();
 }
 
 }  // namespace rankk

@@ -51,17 +51,8 @@ def main():
                                      ws.numel(), N.stream_ptr(dev)), "mi_rank_mirror")
 
         reps = 3 if nq >= 1000 else 10
-        def variant(v, fn):
-            def run():
-                os.environ["MICLIP_MIRROR_VAR"] = v
-                fn()
-                os.environ.pop("MICLIP_MIRROR_VAR")
-            return run
-
         fns = {"mirror_call": mirror_call, "mirror_topk": lambda: mc.topk(q, 10),
-               "exact_f32": lambda: retrieval.rank_topk(corpus, q, 10),
-               "mirror_v1_nopipe": variant("1", mirror_call), "mirror_v2_pf7": variant("2", mirror_call),
-               "mirror_v3_ilv": variant("3", mirror_call)}
+               "exact_f32": lambda: retrieval.rank_topk(corpus, q, 10)}
         times = {name: [] for name in fns}
         for _ in range(rounds):
             for name, fn in fns.items():

@@ -19,7 +19,7 @@ from miclip import retrieval  # noqa: E402
 # default: the certified pass (rank_cert.hip) where eligible (>= 262144 rows, D = 512, k <= 12);
 # exact: MICLIP_RANK_CERT=0, the exact pass alone
 VARIANTS = {"default": {}, "exact": {"MICLIP_RANK_CERT": "0"},
-            "stream12": {"MICLIP_RANK_REG": "0", "MICLIP_RANK_NW": "12", "MICLIP_RANK_CERT": "0"},
+            "stream12": {"MICLIP_RANK_REG": "0", "MICLIP_RANK_CERT": "0"},
             "nomfma": {"MICLIP_RANK_PROBE": "1", "MICLIP_RANK_CERT": "0"},
             # certified-pass timing probes (wrong results): no Gram MFMAs, no MFMAs, no list update
             "c_nogram": {"MICLIP_RANK_CERT_ABL": "1"}, "c_nomfma": {"MICLIP_RANK_CERT_ABL": "2"},
@@ -37,9 +37,8 @@ if os.environ.get("RANK_MICRO_SHAPES") == "cert":   # the certified pass's shape
 
 
 def setenv(v):
-    for k in ("MICLIP_RANK_STAGE1", "MICLIP_RANK_NW", "MICLIP_RANK_REG", "MICLIP_RANK_PROBE", "MICLIP_RANK_ILV",
-              "MICLIP_RANK_PIPE", "MICLIP_RANK_SEED", "MICLIP_RANK_CERT", "MICLIP_RANK_CERT_ABL",
-              "MICLIP_RANK_FOLD"):
+    for k in ("MICLIP_RANK_REG", "MICLIP_RANK_PROBE", "MICLIP_RANK_NB", "MICLIP_RANK_STAMP", "MICLIP_RANK_CERT",
+              "MICLIP_RANK_CERT_ABL", "MICLIP_RANK_FOLD"):
         os.environ.pop(k, None)
     os.environ.update(VARIANTS[v])
 

@@ -1,7 +1,7 @@
 """Short driver for PMC passes over the fused rank kernel: 1M x D f32 corpus,
 Q = 32, k = 10, a few launches (run under rocprofv3 --pmc ...).
 
-  python scripts/rank_pmc.py [D] [reps] [variant env, e.g. MICLIP_RANK_NW=8]
+  python scripts/rank_pmc.py [D] [reps] [variant env, e.g. MICLIP_RANK_NB=9]
 """
 import os
 import sys

@@ -538,3 +538,46 @@ def test_split_merge_bit_identical_to_in_launch_merge(gpu, monkeypatch, N, Q, k,
         monkeypatch.undo()
         torch.cuda.synchronize()
         assert torch.equal(i1, i0) and torch.equal(s1.view(torch.int32), s0.view(torch.int32))
+
+
+@pytest.mark.parametrize("Q", [1, 33])
+@pytest.mark.parametrize("N", [127, 128, 129, 257])
+def test_ring_kernels_tile_round_boundaries(gpu, monkeypatch, N, Q):
+    """The LDS-DMA ring kernels (rank_reg, rank_cert_kernel, rank_mirror_kernel) at the edges
+    of one tile round of their 4-wave workgroup (4 x 32 rows): a last tile one row short, a
+    full round, one row / one round and a row past it, where a wrong tile count, descriptor
+    record count or slot wrap shows first.  Routes of one corpus agree bit for bit: f32 and
+    bf16 rows at D = 512 through the product default (rank_reg) and through the A/B build
+    with the certified pass forced (MICLIP_RANK_CERT=2: rank_cert_kernel + the gated
+    rank_reg), and the fp16 mirror of the f32 rows at D = 512 and at D = 768 (12 chunks per
+    tile against 8 slots: the slot wraps mid-tile) against the exact pass over its master."""
+    import torch
+    from miclip import _native, retrieval, weights
+    from oracle import rank_ref
+    k = 10
+
+    def same(a, b, what):
+        assert torch.equal(a[1], b[1]), what
+        assert torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)), what
+
+    for D in (512, 768):
+        c32 = weights.normal(61, f"rb{N}x{D}", (N, D))
+        q32 = weights.synthetic_corpus(Q, D, seed=62)
+        c, q = _t(c32, gpu), _t(q32, gpu)
+        exact = retrieval.rank_topk(c, q, k)
+        S = rank_ref.scores_ref(c32, q32)
+        for r in range(Q):
+            rank_ref.assert_topk_equivalent(exact[0][r].cpu().numpy(), exact[1][r].cpu().numpy(), S[r], k)
+        mc = retrieval.MirroredCorpus(c)
+        same(mc.topk(q, k), exact, f"mirror D {D}")
+        assert mc.certified >= Q - 1      # random corpora: the certificate holds
+        if D != 512:
+            continue
+        for name, cc, ref in (("f32", c, exact), ("bf16", c.bfloat16(), None)):
+            ref = ref if ref is not None else retrieval.rank_topk(cc, q, k)
+            monkeypatch.setattr(_native, "lib", _native.lib_ab)
+            monkeypatch.setenv("MICLIP_RANK_CERT", "2")
+            cert = retrieval.rank_topk(cc, q, k)
+            monkeypatch.undo()
+            torch.cuda.synchronize()
+            same(cert, ref, f"certified route, {name} rows")
